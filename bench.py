@@ -1,13 +1,23 @@
 #!/usr/bin/env python
 """Benchmark: encoded Mpixels/s of the StreamOptima per-block encode path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR] [--full]
+
+A plain run sets up the workload, runs W untimed and K timed steps, writes the last timed
+step's outputs if --dump-outputs DIR is given (DIR/<name>.npy, float32 / float64; arrays above
+2^20 elements as a fixed seeded sample; the frames are synthetic and seeded, so two runs with
+the same arguments encode the same input) and prints the line: metric, value, unit, ms_per_step
+and the configuration.  Everything else described below -- the `records`, the self-check
+against the oracle's digests (`parity`), `roofline`, `cpu_baseline`, `pcie_inclusive` -- runs
+only with --full, after the same timed steps; a plain line carries `roofline`, `parity`,
+`cpu_baseline` and the PSNR fields as null (not measured, which is not "no fixture" or a
+failure) and has no `records` or `section4_region`.
 
 Workloads (streamoptima_amd/workloads.py, BASELINE.json configs; synthetic splitmix64 frames
 already resident in HBM; bs 16, full-search ME +-16, QP 4, intra_mode 0, nRefFrames 1,
 VBS off):
-  N = 1 (default --config 4k): configs[2], one 4K 30-frame I+P GOP per step; the line also
-        carries a `records.1080p` entry for configs[1] (1920x1080 padded to 1088 rows),
+  N = 1 (default --config 4k): configs[2], one 4K 30-frame I+P GOP per step; with --full the
+        line also carries a `records.1080p` entry for configs[1] (1920x1080 padded to 1088 rows),
         measured the same way in the same run, and `records.<cfg>_x<k>gop` entries: k
         independent GOPs per step with their P-runs interleaved in one persistent launch
         (--gops-in-flight, default 2; a GOP stream's throughput, every GOP parity-checked).
@@ -28,12 +38,12 @@ torch.distributed.run with N ranks BEFORE anything touches the GPU, and every ra
 that WORLD_SIZE == N.  Timing: W untimed steps, then K steps bracketed by barrier +
 synchronize, max over ranks.
 
-After timing (never inside it) the script verifies its own output: the last timed step's
+With --full, after timing (never inside it) the script verifies its own output: the last timed step's
 symbols are digested per frame (streamoptima_amd/digest.py) and compared with the C
 oracle's digests of the same workload (tests/golden/large_gops.json), then one more step
 runs into poisoned output buffers and is compared again.  `parity` in the line reports it.
 
-Prints ONE JSON line on rank 0 (driver contract), including:
+Prints ONE JSON line on rank 0 (driver contract), with --full including:
   roofline      -- the dominant kernel (p_run_kernel, the persistent fused search +
                    transform launch) timed live with HIP events on its stream: the required
                    HBM fraction, plus the VALU busy fraction from PMC counters
@@ -75,6 +85,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every secondary measurement and check (roofline, parity, "
+                         "records, BASELINE.md section 4's region, CPU baseline); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned (every symbol array, the "
+                         "reconstructions, the SSE) to DIR/<name>.npy; arrays above 2^20 elements as a fixed sample")
     ap.add_argument("--record-repeats", type=int, default=3,
                     help="the `records` entries (not the headline) report the median of this many timed K-step runs")
     ap.add_argument("--config", default=None,
@@ -690,6 +706,52 @@ def time_steps(step, world, steps, warmup, dev):
     return max_over_ranks(time.perf_counter() - t0, world), res
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger array: 8 arrays x 2^20 x <= 8 B stays under 64 MB
+# FrameSymbols field -> (file name, dtype that holds every value of the field exactly)
+DUMP_FIELDS = {"split": ("split", np.float32), "mv": ("mv", np.float32), "qtc": ("qtc", np.float32),
+               "tokens": ("tokens", np.float32), "mae_num": ("mae_num", np.float64),
+               "recon": ("recon", np.float32), "sse": ("block_sse", np.float64)}
+
+
+def dump_outputs(res: dict, out_dir: str) -> dict:
+    """Write what the timed step returned (an encode_device-style dict: FrameSymbols per frame and
+    the per-frame SSE) as out_dir/<name>.npy: each symbol field flattened and concatenated in
+    frame order, the per-frame SSE as `sse`.  An array above DUMP_SAMPLE elements is cut to the
+    elements at DUMP_SAMPLE sorted indices (into that concatenation) drawn once from a generator
+    seeded by the field's name, so two runs with the same arguments write the same positions;
+    each frame's elements are picked from that frame, the whole GOP is never concatenated.
+    On N > 1 ranks this is rank 0's share of the output, and the frame pipeline's result has
+    no per-frame SSE yet (its all_reduce runs only in the --full parity pass): no sse.npy."""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    syms = res["symbols"]
+    syms = [syms[k] for k in sorted(syms)] if isinstance(syms, dict) else list(syms)
+    written = {}
+
+    def save(name, parts, dtype):
+        sizes = [p.numel() for p in parts]
+        n = sum(sizes)
+        if n > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.sort(rng.integers(0, n, size=DUMP_SAMPLE))
+            offs = np.concatenate([[0], np.cumsum(sizes)])
+            cuts = np.searchsorted(idx, offs)          # idx[cuts[k]:cuts[k + 1]] fall into parts[k]
+            parts = [p.reshape(-1).index_select(0, torch.from_numpy(idx[a:b] - o).to(p.device))
+                     for p, o, a, b in zip(parts, offs[:-1], cuts[:-1], cuts[1:]) if b > a]
+        a = torch.cat([p.reshape(-1) for p in parts]).cpu().numpy().astype(dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"elements": int(a.size), "of": int(n)}
+
+    for field, (name, dtype) in DUMP_FIELDS.items():
+        parts = [p for p in (getattr(s, field) for s in syms) if torch.is_tensor(p)]
+        if parts:
+            save(name, parts, dtype)
+    if torch.is_tensor(res.get("sse")):
+        save("sse", [res["sse"]], np.float64)
+    return written
+
+
 def run_single(cfg, args, dev, parity: bool):
     """One GOP per step on this GPU (N = 1, or --shard gop at N > 1)."""
     codec = build_codec(cfg, args, dev)
@@ -1017,6 +1079,8 @@ DEFS = {
     "parity": "per-frame sha256 of every symbol array + recon vs the C oracle's digests (tests/golden/large_gops.json); "
               "poisoned = one more step into 0xA5-filled outputs, compared again",
     "records": "other benchmarked configs at 1 GPU, each timed like the headline (median of --record-repeats runs)",
+    "null": "roofline, parity, cpu_baseline and psnr_* are null, records and section4_region absent, in a run "
+            "without --full: not measured there, not failed",
     "detail": "the uncompacted line (notes, per-field sources) is written to --detail-out",
 }
 
@@ -1299,21 +1363,29 @@ def main(argv=None):
                 return senc.encode(frames, cfg["intra_dur"], cfg["qp"])
             elapsed, res = time_steps(step, world, args.steps, args.warmup, dev)
 
+    # ---- --dump-outputs: the last timed step's result, before anything below reuses its buffers ----
+    if args.dump_outputs and rank == 0:
+        wrote = dump_outputs(res, args.dump_outputs)
+        print(f"bench.py: --dump-outputs {args.dump_outputs}: " +
+              ", ".join(f"{k} {v['elements']}/{v['of']}" for k, v in wrote.items()), file=sys.stderr, flush=True)
+
+    # ---- everything from here to the line is --full: a plain run only times the steps ----
     # ---- right after timing (GPU still at its working clock): the dominant kernel's roofline ----
     rl = None
-    if (rank == 0 and not args.cpu_plumbing and cfg.get("me", "full") == "full" and codec.engine().pipelined_ok(1)
+    if (args.full and rank == 0 and not args.cpu_plumbing and cfg.get("me", "full") == "full" and codec.engine().pipelined_ok(1)
             and not cfg.get("rc")):
         # stripe mode: the kernel is timed on rank 0's GPU alone over the full frame (a
         # one-GPU GOP supplies the reference reconstructions it replays)
         syms = res["symbols"] if not stripe else codec.encode_device(frames, cfg["intra_dur"])["symbols"]
         rl = kernel_roofline(codec, frames, syms, args.kernel_reps, components=not cfg.get("vbs"))
     rl_rc = None
-    if rank == 0 and not args.cpu_plumbing and cfg.get("rc", 0) >= 3 and not stripe and codec.engine().pipelined_ok(1):
+    if (args.full and rank == 0 and not args.cpu_plumbing and cfg.get("rc", 0) >= 3 and not stripe
+            and codec.engine().pipelined_ok(1)):
         rl_rc = rc_roofline(codec, frames, res["symbols"], args.kernel_reps, name)
 
     # ---- after timing: parity of the timed output ----
     parity = None
-    if parity_ok and not args.cpu_plumbing:
+    if args.full and parity_ok and not args.cpu_plumbing:
         if fenc is not None:
             fenc.check()
             res["sse"] = fenc.sse(res["symbols"], f)
@@ -1343,12 +1415,12 @@ def main(argv=None):
     barrier(world)
 
     fallback = None
-    if (world == 1 and not args.cpu_plumbing and codec is not None and cfg.get("me", "full") == "full"
+    if (args.full and world == 1 and not args.cpu_plumbing and codec is not None and cfg.get("me", "full") == "full"
             and not cfg.get("rc") and codec.engine().pipelined_ok(1)):
         fallback = dense_fallback_of(codec.engine(), cfg, step)
 
     psnr_mean = None
-    if "sse" in res:
+    if args.full and res.get("sse") is not None:
         hp = -(-h // 16) * 16
         sse = res["sse"].cpu().numpy()
         vals = [10 * np.log10(255 ** 2 / (s / (hp * w))) for s in sse if s > 0]
@@ -1375,10 +1447,11 @@ def main(argv=None):
     # BASELINE.md section 4's region first, right after the headline (a run of records ahead of it
     # left the region 1.6x slower on one box: profiles/r05/pcie_order.log)
     pcie = None
-    if rank == 0 and world == 1 and not args.cpu_plumbing and not args.no_pcie and plain_cfg and not args.pcie_last:
+    if (args.full and rank == 0 and world == 1 and not args.cpu_plumbing and not args.no_pcie and plain_cfg
+            and not args.pcie_last):
         pcie = guarded("pcie_inclusive", lambda: pcie_inclusive(codec, cfg, frames))
     records = None
-    if rank == 0 and world == 1 and not args.cpu_plumbing and not args.no_records and name == "4k":
+    if args.full and rank == 0 and world == 1 and not args.cpu_plumbing and not args.no_records and name == "4k":
         records = {"1080p": guarded("records.1080p", lambda: record_single("1080p", args, dev))}
         for k in args.gops_in_flight:
             for nm in ("1080p", "4k"):
@@ -1391,13 +1464,14 @@ def main(argv=None):
         # ROI + two-pass rate-control GOP, each measured and parity-checked like the headline
         for nm in ("4k_vbs", "4k_rc2pass"):
             records[nm] = guarded(f"records.{nm}", lambda nm=nm: record_single(nm, args, dev))
-    if rank == 0 and world == 1 and not args.cpu_plumbing and not args.no_pcie and plain_cfg and args.pcie_last:
+    if (args.full and rank == 0 and world == 1 and not args.cpu_plumbing and not args.no_pcie and plain_cfg
+            and args.pcie_last):
         pcie = guarded("pcie_inclusive", lambda: pcie_inclusive(codec, cfg, frames))
     if rank == 0 and args.cpu_plumbing and args.inject_failure and not any(
             d["what"] == args.inject_failure for d in degraded):   # the mechanism, on a CPU-only host
         records = {args.inject_failure: guarded(args.inject_failure, lambda: {"plumbing": True})}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.cpu_plumbing:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.cpu_plumbing:
         cpu = guarded("cpu_baseline", lambda: cpu_baseline(cfg, args.cpu_rows, args.cpu_pool_rows))
     if rank != 0:
         barrier(world)

@@ -6,8 +6,8 @@ candidate (`cur`, sea2_tile's first count), the least SAD among the 4 smallest b
 (`top4`), among each quadrant's smallest bound (`quad`), the 16 smallest, and the block
 minimum (`ideal`, the floor any U can reach).  Usage: python tests/analysis/sea_refine.py F
 """
-import numpy as np, sys
-sys.path.insert(0, "/root/repo")
+import numpy as np, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from streamoptima_amd.synth import synth_sequence
 from oracle import oracle as O
 h, w = 160, 3840

@@ -2,8 +2,8 @@
 Offline survivor statistics of the exact SEA pruning in me_sea2_kernel (so_me.hip) on the
 bench content: per block, count the candidates whose 4x4-sum lower bound does not exceed the
 SAD of the smallest-bound candidate.  Uses the C oracle for the I-frame reconstruction."""
-import numpy as np, sys
-sys.path.insert(0, "/root/repo")
+import numpy as np, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from streamoptima_amd.synth import synth_sequence
 from oracle import oracle as O
 h, w = 272, 480

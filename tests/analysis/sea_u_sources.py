@@ -8,11 +8,12 @@ P-frame F of the bench GOP (reference = the oracle's reconstruction chain), unde
 Prints the mean survivors, the mean 16-candidate passes (blocks with > 4 survivors:
 ceil(n / 16); <= 4 and 1 take one partial pass / none) and the > 192 fraction.
 Usage: python tests/analysis/sea_u_sources.py [F] [H]"""
+import os
 import sys
 
 import numpy as np
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from numpy.lib.stride_tricks import sliding_window_view  # noqa: E402
 
 from oracle import oracle as O  # noqa: E402
