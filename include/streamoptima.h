@@ -136,6 +136,14 @@ int so_encode_p_rows(const uint8_t* cur, const uint8_t* const* refs, int nref, i
  *                            is zero).  Faster where most blocks are zero (flat content), a
  *                            little slower elsewhere; default 0.  The Python engine sets it per
  *                            run from the previous run's share of all-zero blocks.
+ *   SO_OPT_RUN_TALL_TILES    the tile of the one-GPU plain run (so_encode_p_run / _runs, VBS off, no
+ *                            test hook set): 128 x 48 px (24 blocks: six of the workgroup's eight
+ *                            waves transform, and a tile's window halo is smaller) or the
+ *                            128 x 32 px of every other run.  -1 (default, "unset"): 48 rows when
+ *                            the frames in flight offer at least as many 48-row tiles as the
+ *                            grid has resident workgroups (4K: yes; 1080p: no, it stays on the
+ *                            32-row tile, whose tile step is shorter); 0: never; 1: always.
+ *                            Exact either way.  so_p_run_tile_rows reports the choice.
  * so_set_option returns SO_E_INVALID for an unknown option or a value out of range.
  */
 #define SO_OPT_RUN_2PASS_FUSED 1
@@ -153,6 +161,7 @@ int so_encode_p_rows(const uint8_t* cur, const uint8_t* const* refs, int nref, i
  * product kernels carry neither hook. */
 #define SO_OPT_TEST_LOSE_FLAG 6
 #define SO_OPT_RUN_ZERO_SKIP 7
+#define SO_OPT_RUN_TALL_TILES 8
 int so_set_option(int option, int value);
 int so_get_option(int option);
 
@@ -224,6 +233,10 @@ int so_p_run_resident_workgroups(int vbs);
  * 0 and 2).  so_p_run_resident_workgroups(vbs) is the smallest of these, so a claim sized by it
  * fits whichever kernel a rank launches.  SO_E_INVALID for another mode or a failed query. */
 int so_p_run_mode_resident_workgroups(int mode, int vbs);
+/* Block rows per tile, 2 or 3, that a one-GPU plain run of H x W frames with `conc` independent
+ * runs interleaved (so_encode_p_run: 1) would use on the calling thread's current device under
+ * the current SO_OPT_RUN_TALL_TILES.  SO_E_INVALID for a bad shape or a failed device query. */
+int so_p_run_tile_rows(int H, int W, int conc);
 int so_encode_p_run(const uint8_t* const* curs, int nframes, const uint8_t* ref0, int H, int W,
                     int bs, int sr, int qp_rd, const int32_t* qp_row, int vbs, double lam,
                     uint8_t* const* out_split,

@@ -42,6 +42,7 @@ _SIGS = {
     "so_p_run_resident_workgroups": ([_i], _i),
     "so_p_run_mode_resident_workgroups": ([_i, _i], _i),
     "so_p_run_2pass_fused": ([_i, _i], _i),
+    "so_p_run_tile_rows": ([_i, _i, _i], _i),
     "so_encode_p_run": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                         _i),
     "so_encode_p_run_2pass": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -103,6 +104,7 @@ TOKENS_ONLY = 2
 # so_set_option (include/streamoptima.h SO_OPT_*)
 OPT_RUN_2PASS_FUSED, OPT_FASTME_SERIAL, OPT_FASTME_SEGMENT, OPT_FASTME_WARMUP, OPT_COUNT_SAD_OPS = 1, 2, 3, 4, 5
 OPT_RUN_ZERO_SKIP = 7
+OPT_RUN_TALL_TILES = 8   # -1 (default): chosen per launch, 0: never, 1: always
 OPT_TEST_LOSE_FLAG = 6
 
 EXPORTED = tuple(_SIGS)

@@ -200,6 +200,53 @@ SO_DEV void xform2d_rows(double* lds, int l, const T* in_row, double* out_row, c
     wave_sync();   // lds free for reuse
 }
 
+// xform2d_rows<16, INVERSE, int> through half its LDS at full width: a 16 x 17 DWORD scratch.
+// The int32 first transpose fits it as it stands; the second one, of doubles, goes through it
+// in two rounds -- every lane's low dwords, then every lane's high dwords -- so all 16 lanes
+// work in both rounds (unlike the 16 x 9 double forms below, where half the lanes idle per
+// half).  The doubles are reassembled from the same bits: the arithmetic is xform2d_rows' bit
+// for bit.  Pitch 17 dwords and 272 dwords per block: the four blocks of a wave sit 16 banks
+// apart, so both the column writes and the row reads are conflict free.
+template <bool INVERSE, class TWt>
+SO_DEV void xform2d_rows_dw(double* lds, int l, const int* in_row, double* out_row, const TWt& tw) {
+    constexpr int N = 16, P = N + 1;
+    // the lane's row and column as two LDS addresses behind an optimisation barrier: every
+    // access below is then one of them plus an immediate (ds_read2 / ds_write2 offsets), instead
+    // of an address register per pair held across both transforms
+    typedef __attribute__((address_space(3))) uint32_t* lds_u32p;
+    lds_u32p rowp = (lds_u32p)(reinterpret_cast<uint32_t*>(lds) + l * P);
+    lds_u32p colp = (lds_u32p)(reinterpret_cast<uint32_t*>(lds) + l);
+    asm volatile("" : "+v"(rowp), "+v"(colp));
+    double v[N];
+    {
+#pragma unroll
+        for (int c = 0; c < N; ++c) rowp[c] = (uint32_t)in_row[c];
+        wave_sync();
+        int x[N];
+#pragma unroll
+        for (int r = 0; r < N; ++r) x[r] = (int)colp[r * P];
+        wave_sync();   // every lane's int reads before the dwords below overwrite them
+        if constexpr (INVERSE) dct::dct3_16_i(x, v, tw); else dct::dct2_16_i(x, v, tw);   // axis 0 (columns)
+    }
+    uint32_t lo[N];
+#pragma unroll
+    for (int r = 0; r < N; ++r) colp[r * P] = (uint32_t)__builtin_bit_cast(uint64_t, v[r]);
+    wave_sync();
+#pragma unroll
+    for (int c = 0; c < N; ++c) lo[c] = rowp[c];
+    wave_sync();   // every lane's low dwords read before the high ones overwrite them
+#pragma unroll
+    for (int r = 0; r < N; ++r) colp[r * P] = (uint32_t)(__builtin_bit_cast(uint64_t, v[r]) >> 32);
+    wave_sync();
+#pragma unroll
+    for (int c = 0; c < N; ++c)
+        v[c] = __builtin_bit_cast(double, ((uint64_t)rowp[c] << 32) | (uint64_t)lo[c]);
+    if constexpr (INVERSE) dct::dct3<N>(v, tw); else dct::dct2<N>(v, tw);   // axis 1 (rows)
+#pragma unroll
+    for (int c = 0; c < N; ++c) out_row[c] = v[c];
+    wave_sync();   // lds free for reuse
+}
+
 // The forward xform2d_rows<16, false> of integer rows through half its LDS (16 x 9 doubles): the
 // int32 transpose fits the scratch whole (16 x 17 words), the FP64 one goes back to rows in two
 // halves (as xform2d_rows_half).  The same operations as xform2d_rows bit for bit (the column

@@ -26,10 +26,14 @@ void set_error(const char* fmt, ...) {
 }
 
 // so_set_option / so_get_option (SO_OPT_*): index = option id
-static std::atomic<int> g_opt[8] = {0, 1, 0, 32, 32, 0, 0, 0};   // SO_OPT_RUN_2PASS_FUSED on by default
+// SO_OPT_RUN_2PASS_FUSED on by default, SO_OPT_RUN_TALL_TILES unset (-1: chosen per launch)
+#ifndef SO_RUN_TALL_DEFAULT   // A/B builds: 0 = the 32-row twin unless the option is set
+#define SO_RUN_TALL_DEFAULT -1
+#endif
+static std::atomic<int> g_opt[9] = {0, 1, 0, 32, 32, 0, 0, 0, SO_RUN_TALL_DEFAULT};
 
 int option(int id) {
-    return (id > 0 && id < 8) ? g_opt[id].load(std::memory_order_relaxed) : 0;
+    return (id > 0 && id < 9) ? g_opt[id].load(std::memory_order_relaxed) : 0;
 }
 
 int me_launch(const uint8_t* cur, const RefSet& refs, int nref, int H, int W, int bs, int sr, int by0, int by1,
@@ -327,6 +331,7 @@ int so_set_option(int opt, int value) {
     const bool ok = (opt == SO_OPT_RUN_2PASS_FUSED || opt == SO_OPT_FASTME_SERIAL || opt == SO_OPT_COUNT_SAD_OPS ||
                      opt == SO_OPT_RUN_ZERO_SKIP)
                         ? (value == 0 || value == 1)
+                    : opt == SO_OPT_RUN_TALL_TILES                               ? (value >= -1 && value <= 1)
                     : opt == SO_OPT_FASTME_SEGMENT                               ? value >= 1
                     : opt == SO_OPT_FASTME_WARMUP || opt == SO_OPT_TEST_LOSE_FLAG ? value >= 0
                                                                                  : false;
@@ -434,6 +439,19 @@ int so_p_run_resident_workgroups(int vbs) {
     const int n = p_run_capacity(vbs ? 1 : 0);
     if (n <= 0) {
         set_error("so_p_run_resident_workgroups: device query failed");
+        return SO_E_INVALID;
+    }
+    return n;
+}
+
+int so_p_run_tile_rows(int H, int W, int conc) {
+    if (H < 16 || W < 128 || H % 16 != 0 || W % 128 != 0 || conc < 1) {
+        set_error("so_p_run_tile_rows: H %d W %d conc %d (H a multiple of 16, W of 128, conc >= 1)", H, W, conc);
+        return SO_E_INVALID;
+    }
+    const int n = p_run_tile_rows(H, W, conc);
+    if (n <= 0) {
+        set_error("so_p_run_tile_rows: device query failed");
         return SO_E_INVALID;
     }
     return n;

@@ -22,6 +22,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #include "so_block.h"
@@ -630,8 +631,9 @@ int me_fme_launch(const uint8_t* cur, const uint8_t* planes, size_t pstride, int
                              // dense blocks 8.9 -> 3.8 %; 768: 161.5, profiles/r03/r03n/vbs_ab.log)
 #endif
 #ifndef SO_DENSE_THR     // a tile searches dense from the start when the same tile of the
-#define SO_DENSE_THR 8   // reference frame had at least this many of its 16 blocks overflow,
-#endif                   // except every SO_DENSE_PROBE-th frame, which probes the bound again
+#define SO_DENSE_THR 8   // reference frame had at least this many of its 16 blocks overflow (a
+#endif                   // 24-block tile: 12, the same half), except every SO_DENSE_PROBE-th frame,
+                         // which probes the bound again
 #ifndef SO_DENSE_PROBE    // round 6, 4 -> 16: a probe frame pays the bound and the lists of every
 #define SO_DENSE_PROBE 16 // block before their dense search -- noise 3.13 -> 2.94 ms per 4K GOP (8:
 #endif                    // 3.01, 32: 2.91), textured content unchanged (ab_dense_probe_period.log)
@@ -646,19 +648,26 @@ int me_fme_launch(const uint8_t* cur, const uint8_t* planes, size_t pstride, int
 #endif
 // NW_ waves per workgroup: 8 (two blocks per wave; me_sea2_kernel) or 16 (one block per
 // wave; p_tile_kernel at 8 waves/SIMD)
-// TPX_: tile width, 128 (16 blocks)
-template <int NW_, int TPX_ = 128>
+// TPX_: tile width, 128 (8 blocks per block row)
+// TBY_: block rows per tile, 2 (16 blocks: waves 0-3 transform) or 3 (the one-GPU plain run's tall
+// tile, 24 blocks: waves 0-5 transform, and the window's halo is 2.08x instead of 2.5x the tile)
+// TQDW_: the fused tile's transform scratch is 16 x 17 dwords per block (xform2d_rows_dw)
+// instead of 16 x 17 doubles -- what lets 24 blocks fit three workgroups per CU
+template <int NW_, int TPX_ = 128, int TBY_ = 2, bool TQDW_ = false>
 struct Sea2GeoT {
     static constexpr int SR = 16, NT = 17;
-    static constexpr int TPX = TPX_, TBX = TPX / 16, TPY = 32, TBY = 2;
-    static constexpr int WR = TPY + 2 * SR;               // 64 window rows
+    static constexpr int TPX = TPX_, TBX = TPX / 16, TBY = TBY_, TPY = 16 * TBY;
+    static constexpr bool TQDW = TQDW_;
+    static constexpr int WR = TPY + 2 * SR;               // 64 (80) window rows
     static constexpr int WD = (TPX + 2 * SR) / 4;         // 40 (24) data dwords per row
     static constexpr int RP = WD + 1;                     // pitch 41 (25)
     static constexpr int B4R = WR - 3, B4C = TPX + 2 * SR - 3, B4P = 4 * RP;   // 41 dwords: rows 16 apart land 16 banks apart
     // transform phase: blocks per wave (16 lanes each); 4 (waves 0-3 for 16 blocks) or 2
     // (waves 0-3 for 8 blocks: half the per-wave latency)
     static constexpr int TQ_BPW = TPX == 128 ? 4 : 2;
-    static constexpr int B4BAND = NW_ >= 16 ? 3 : 6;      // output rows per byte-sum thread
+    // output rows per byte-sum thread, so that WD * B4NB <= NTHREADS (80 window rows: 11 bands of
+    // 7, the last ending on the window's last row)
+    static constexpr int B4BAND = TBY_ == 3 ? 7 : (NW_ >= 16 ? 3 : 6);
     static constexpr int B4NB = (B4R + B4BAND - 1) / B4BAND;
     static constexpr int B4RS = B4NB * B4BAND;            // stored rows: whole bands, no bounds tests
     static constexpr int NBLK = TBX * TBY;
@@ -1250,24 +1259,33 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
 
     SO_MARK(stage_cur);
     for (int i = tid; i < G::NBLK * (VBS ? 5 : 1); i += G::NTHREADS) keys[i] = kNoKey;
-    // interior window (uniform): thread = (row, column phase) with immediate per-dword offsets
+    // interior window (uniform): thread = (row, column phase) with immediate per-dword offsets.
+    // WTPR threads per row; where the rows do not divide the workgroup (80 rows: 6 threads per
+    // row, 480 of 512) the last threads stage nothing (WALL: every thread has a row)
     constexpr int WTPR = G::NTHREADS / G::WR, WNPT = (RP + WTPR - 1) / WTPR;
-    static_assert(G::NTHREADS % G::WR == 0, "window staging");
+    constexpr bool WALL = WTPR * G::WR == G::NTHREADS;
+    static_assert(WTPR >= 1 && WTPR * WNPT >= RP, "window staging");
     const int wwr = tid / WTPR, wc0 = tid - wwr * WTPR;
     const bool win_int = x0 - SR >= 0 && x0 - SR + 4 * RP <= W && y0 - SR >= 0 && y0 - SR + G::WR <= H;
     if (x0 + CP <= W && y0 + G::TPY <= H) {
         // interior tile (uniform branch): thread = (row, column phase); the loads' and stores'
         // per-dword offsets are immediates, so staging costs a few VALU per thread
-        constexpr int TPR = G::NTHREADS / G::TPY, NPT = (CP / 4) / TPR;   // threads per row, dwords per thread
-        static_assert(G::NTHREADS % G::TPY == 0 && (CP / 4) % TPR == 0, "current-tile staging");
+        // threads per row, dwords per thread; CALL: the rows divide the workgroup and the
+        // threads of a row its dwords (48 rows: 10 threads per row, 480 of 512, 4 dwords each
+        // with the row's last two threads short of one)
+        constexpr int TPR = G::NTHREADS / G::TPY, NPT = (CP / 4 + TPR - 1) / TPR;
+        constexpr bool CALL = G::NTHREADS % G::TPY == 0 && (CP / 4) % TPR == 0;
+        static_assert(TPR >= 1 && TPR <= CP / 4, "current-tile staging");
         SO_MARK(stage_cur_int);
         const int rr = tid / TPR, c0 = tid - rr * TPR;
         const uint32_t* src = reinterpret_cast<const uint32_t*>(cur + (size_t)(y0 + rr) * W + x0) + c0;
         uint32_t v[NPT];
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) v[k] = src[k * TPR];
+        for (int k = 0; k < NPT; ++k)
+            if (CALL || (rr < G::TPY && c0 + k * TPR < CP / 4)) v[k] = src[k * TPR];
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) curt[rr * G::CPD + c0 + k * TPR] = v[k];
+        for (int k = 0; k < NPT; ++k)
+            if (CALL || (rr < G::TPY && c0 + k * TPR < CP / 4)) curt[rr * G::CPD + c0 + k * TPR] = v[k];
     } else {   // current tile (zero outside the frame / stripe)
         SO_MARK(stage_cur_edge);
         constexpr int N = G::TPY * CP / 4, IT = (N + G::NTHREADS - 1) / G::NTHREADS;
@@ -1326,10 +1344,10 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             const uint32_t* src = reinterpret_cast<const uint32_t*>(ref + (size_t)(y0 - SR + wwr) * W + (x0 - SR)) + wc0;
 #pragma unroll
             for (int k = 0; k < WNPT; ++k)
-                if (wc0 + k * WTPR < RP) wv0[k] = src[k * WTPR];
+                if ((WALL || wwr < G::WR) && wc0 + k * WTPR < RP) wv0[k] = src[k * WTPR];
 #pragma unroll
             for (int k = 0; k < WNPT; ++k)
-                if (wc0 + k * WTPR < RP) win[wwr * RP + wc0 + k * WTPR] = wv0[k];
+                if ((WALL || wwr < G::WR) && wc0 + k * WTPR < RP) win[wwr * RP + wc0 + k * WTPR] = wv0[k];
         } else {   // window: all loads first, then the LDS stores (zero outside the frame)
             SO_MARK(stage_win_edge);
             constexpr int N = G::WR * RP, IT = (N + G::NTHREADS - 1) / G::NTHREADS;
@@ -1782,6 +1800,12 @@ constexpr int kTqScratch = 16 * 17;
 #define SO_PTILE_TOK_HALF 1
 #endif
 constexpr int kTqScratchHalf = 16 * 9;
+// a geometry with TQDW: 16 x 17 dwords per block (xform2d_rows_dw, both transforms), in doubles
+constexpr int kTqScratchDw = 16 * 17 / 2;
+template <class G, bool HALFTQ>
+constexpr int tq_scratch() {
+    return HALFTQ ? kTqScratchHalf : (G::TQDW ? kTqScratchDw : kTqScratch);
+}
 // SO_FWD_MFMA=1: the fused tiles' forward transform on the matrix cores with an exactness
 // certificate (fwd_mfma).  Bit-exact (the GPU suite passes through it) but measured slower, so
 // off: 73.6 vs 67.0 us per 4K P-frame -- the FP32 MFMA runs at the FP32 vector rate and does not
@@ -1794,7 +1818,7 @@ template <class G, bool HALFTQ = false>
 struct PTileGeo {
     static constexpr int B4 = (G::B4RS * G::B4P + 4) / 4;             // dwords
     static constexpr int LIST = G::NW * G::CAPL / 2;                  // dwords
-    static constexpr int TQD = G::NBLK * (HALFTQ ? kTqScratchHalf : kTqScratch);   // doubles
+    static constexpr int TQD = G::NBLK * tq_scratch<G, HALFTQ>();   // doubles
     static constexpr int U64 = ((B4 + LIST + 1) / 2 > TQD) ? (B4 + LIST + 1) / 2 : TQD;
 };
 // VBSEnable (tq16_vbs): 16 x 18 doubles per block (the 16 x 17 transpose of the block, or the
@@ -1933,6 +1957,8 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
             static_assert(!HALFTQ || TOK, "the half scratch carries the forward transform only");
             if constexpr (HALFTQ)
                 xform2d_fwd_i_half(dl, l, res, tcr, SO_TQ_TW());
+            else if constexpr (G::TQDW)
+                xform2d_rows_dw<false>(dl, l, res, tcr, SO_TQ_TW());
             else
                 xform2d_rows<16, false>(dl, l, res, tcr, SO_TQ_TW());
             SO_MARK(tq_quant);
@@ -1978,9 +2004,17 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
             SO_MARK(tq_sse_records);
             int e2 = 0;
             if (o.sse) {
+                // TQDW: the current row's address is recomputed here -- held across the dword
+                // transposes it was spilled, and its reload waited for the row store above
+                const uint32_t* crow2 = crow;
+                if constexpr (G::TQDW) {
+                    int g2 = g, l2 = l;
+                    asm volatile("" : "+v"(g2), "+v"(l2));
+                    crow2 = S.curt + ((g2 / TBX) * 16 + l2) * G::CPD + (g2 % TBX) * 4;
+                }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const uint32_t cw = crow[k];
+                    const uint32_t cw = crow2[k];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int d = (int)((cw >> (8 * e)) & 255) - (rec[4 * k + e] & 255);
@@ -1996,7 +2030,10 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
             double rd[16];
             dequant_row_int<16>(q, l, qpr, dq);
             SO_MARK(tq_inv);
-            xform2d_rows<16, true>(dl, l, dq, rd, SO_TQ_TW());
+            if constexpr (G::TQDW)
+                xform2d_rows_dw<true>(dl, l, dq, rd, SO_TQ_TW());
+            else
+                xform2d_rows<16, true>(dl, l, dq, rd, SO_TQ_TW());
             SO_MARK(tq_recon);
             int rec[16];
             {
@@ -2030,11 +2067,22 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
         } else {
             sse = full();
         }
-        if (l < 12) o.mv[b * 12 + l] = (int16_t)(l == 0 ? dx : l == 1 ? dy : l == 2 ? rf : 0);
+        int mdx = dx, mdy = dy, mrf = rf, msad = sad;
+        if constexpr (G::TQDW) {   // the record re-read from LDS (as the row address above)
+            int g2 = g;
+            asm volatile("" : "+v"(g2));
+            lds_vu32p mp = (lds_vu32p)reinterpret_cast<const uint32_t*>(&S.mer[g2]);
+            const uint32_t w0 = mp[0], w1 = mp[1];
+            mdx = (int)(int16_t)(w0 & 0xFFFFu);
+            mdy = (int)w0 >> 16;
+            mrf = (int)(int16_t)(w1 & 0xFFFFu);
+            msad = (w1 >> 16) == 0xFFFFu ? -1 : (int)(w1 >> 16);
+        }
+        if (l < 12) o.mv[b * 12 + l] = (int16_t)(l == 0 ? mdx : l == 1 ? mdy : l == 2 ? mrf : 0);
         if (l == 0) {
             o.split[b] = 0;
             o.tokens[b] = tok;
-            o.mae[b] = sad;
+            o.mae[b] = msad;
             if (o.sse) o.sse[b] = sse;
         }
     }
@@ -2607,7 +2655,7 @@ SO_DEV void ptile_body(PTileLds<G, VBS, HALFTQ>& S, int tile, const uint8_t* __r
                 tq16_vbs_fwd<G, SC1, HALO>(S, gq, ln & 15, S.un + gq * kTqScratchVbs, bx0, byt0, nbx, by0, by1, W, qp_rd,
                                            qp_row, qp_map, lam, o);
             else
-                tq16_exact<G, SC1, HALO, TOK, HALFTQ, ZSKIP>(S, gq, ln & 15, S.un + gq * (HALFTQ ? kTqScratchHalf : kTqScratch), bx0,
+                tq16_exact<G, SC1, HALO, TOK, HALFTQ, ZSKIP>(S, gq, ln & 15, S.un + gq * tq_scratch<G, HALFTQ>(), bx0,
                                               byt0, nbx, by0, by1, W, qp_rd,
                                               qp_row, qp_map, o, hl, qs);
         }
@@ -3084,18 +3132,28 @@ SO_DEV uint32_t run_dequeue(uint32_t* ws) {
 // one-GPU uniform-QP VBS run the same slot selects the latency-bound twin: its VBS survivor lists
 // built one ballot per candidate row (sea2_tile's LISTS = 2; the host launches it when the grid
 // has more slots than a frame has tiles), the other one building them from lane masks (LISTS = 1)
-template <int NW, int MODE, bool VBS = false, bool HOOKS = false, bool UQP = false, bool ZSKIP = false>
-__global__ void __launch_bounds__(NW * 64)
-__attribute__((amdgpu_waves_per_eu(VBS ? SO_VBS_WPE : (NW >= 16 ? SO_PTILE_WPE16 : SO_SEA2_WPE))))
-p_run_kernel(const PRunArgs a, int nframes, const uint8_t* __restrict__ ref0, int H, int W,
-             int qp_rd, const int32_t* __restrict__ qp_row_arg, uint32_t* __restrict__ ws, int ws_stamp_base,
-             const PRunStripe sp, double lam) {
+// G: the tile geometry.  The one-GPU plain run without hooks (and its zero-skip twin) has two
+// kernels sharing this body: p_run_kernel on 128 x 48 tiles (24 blocks, the dword transform
+// scratch) and p_run_short_kernel on the 128 x 32 tiles of every other run; the host picks per
+// launch (p_run_tall_choice).
+#ifndef SO_RUN_SHORT_TQDW   // A/B builds: the short plain run's transforms through the dword scratch
+#define SO_RUN_SHORT_TQDW 0  // (xform2d_rows_dw alone, on 32-row tiles)
+#endif
+template <int NW>
+using RunGeoTall = Sea2GeoT<NW, 128, 3, true>;
+template <int NW>
+using RunGeoShort = Sea2GeoT<NW, 128, 2, SO_RUN_SHORT_TQDW != 0>;
+template <int MODE, bool VBS, bool HOOKS, bool UQP>
+constexpr bool kRunHasTall = MODE == kRunSingle && !VBS && !HOOKS && !UQP;
+template <class G, int MODE, bool VBS, bool HOOKS, bool UQP, bool ZSKIP>
+SO_DEV void p_run_body(const PRunArgs& a, int nframes, const uint8_t* __restrict__ ref0, int H, int W,
+                       int qp_rd, const int32_t* __restrict__ qp_row_arg, uint32_t* __restrict__ ws, int ws_stamp_base,
+                       const PRunStripe& sp, double lam) {
     static_assert(!UQP || VBS, "the uniform-QP instantiation is the VBS run's");
     static_assert(!ZSKIP || (MODE == kRunSingle && !HOOKS && (!VBS || UQP)),
                   "the zero-skip / latency-lists instantiation is the one-GPU run's");
     constexpr int LISTS = VBS && MODE == kRunSingle && UQP ? (ZSKIP ? 2 : 1) : 0;
     const int32_t* __restrict__ const qp_row = UQP ? nullptr : qp_row_arg;
-    using G = Sea2GeoT<NW>;
     __shared__ PTileLds<G, VBS> S;
     __shared__ int s_task;
     __shared__ int s_dense;   // kRunSingle: this tile searches dense (sea2_tile's dense_flag)
@@ -3273,7 +3331,7 @@ p_run_kernel(const PRunArgs a, int nframes, const uint8_t* __restrict__ ref0, in
             // which probes the bound again
             if (MODE == kRunSingle && dep >= 0 && (f & (SO_DENSE_PROBE - 1)) != 0) {
                 const uint32_t fb = (uint32_t)__builtin_amdgcn_readlane((int)raw, 9);
-                if (lane == 0) s_dense = fb >= (uint32_t)SO_DENSE_THR ? 1 : 0;
+                if (lane == 0) s_dense = fb >= (uint32_t)(SO_DENSE_THR * G::NBLK / 16) ? 1 : 0;
             }
         };
         // ptile_body's `post`: the next task's dequeue, before the tile's drain (one-GPU,
@@ -3506,6 +3564,28 @@ p_run_kernel(const PRunArgs a, int nframes, const uint8_t* __restrict__ ref0, in
 #undef ep
 #endif
 
+#define SO_RUN_KERNEL_ATTRS(NW, VBS) \
+    __launch_bounds__(NW * 64)       \
+    __attribute__((amdgpu_waves_per_eu(VBS ? SO_VBS_WPE : (NW >= 16 ? SO_PTILE_WPE16 : SO_SEA2_WPE))))
+template <int NW, int MODE, bool VBS = false, bool HOOKS = false, bool UQP = false, bool ZSKIP = false>
+__global__ void SO_RUN_KERNEL_ATTRS(NW, VBS)
+p_run_kernel(const PRunArgs a, int nframes, const uint8_t* __restrict__ ref0, int H, int W,
+             int qp_rd, const int32_t* __restrict__ qp_row_arg, uint32_t* __restrict__ ws, int ws_stamp_base,
+             const PRunStripe sp, double lam) {
+    using G = std::conditional_t<kRunHasTall<MODE, VBS, HOOKS, UQP>, RunGeoTall<NW>, Sea2GeoT<NW>>;
+    p_run_body<G, MODE, VBS, HOOKS, UQP, ZSKIP>(a, nframes, ref0, H, W, qp_rd, qp_row_arg, ws, ws_stamp_base, sp, lam);
+}
+// the 32-row twin of the one-GPU plain run (p_run_kernel<NW, kRunSingle, false, false, false, ZSKIP>)
+template <int NW, bool ZSKIP>
+__global__ void SO_RUN_KERNEL_ATTRS(NW, false)
+p_run_short_kernel(const PRunArgs a, int nframes, const uint8_t* __restrict__ ref0, int H, int W,
+                   int qp_rd, const int32_t* __restrict__ qp_row_arg, uint32_t* __restrict__ ws, int ws_stamp_base,
+                   const PRunStripe sp, double lam) {
+    p_run_body<RunGeoShort<NW>, kRunSingle, false, false, false, ZSKIP>(a, nframes, ref0, H, W, qp_rd, qp_row_arg, ws,
+                                                                         ws_stamp_base, sp, lam);
+}
+#undef SO_RUN_KERNEL_ATTRS
+
 // [kRunDoneBase, +kRunMax * ntiles64) done flags, then (two-pass runs) kRunMax * ntiles128
 // pass-1 done flags and kRunMax * nb pass-1 token counts
 static size_t run_tiles(int H, int W, int tbx, int tby) {
@@ -3528,6 +3608,9 @@ constexpr size_t kLdsPerCuObserved = 161280;   // gfx950: 3 x 53,760 B resident 
 // scalars) stays within 53,760 B: a later LDS increase must not silently drop it to two
 static_assert(sizeof(PTileLds<Sea2GeoT<SO_PTILE_NW>, true>) + 64 <= kLdsPerCuObserved / 3,
               "the VBS run's LDS no longer fits three workgroups per gfx950 CU");
+// so is the tall plain run: its 24 blocks fit only through the dword transform scratch
+static_assert(sizeof(PTileLds<RunGeoTall<SO_PTILE_NW>>) + 64 <= kLdsPerCuObserved / 3,
+              "the tall plain run's LDS no longer fits three workgroups per gfx950 CU");
 static int run_shape(const void* kernel, int* ncu, int* per_cu) {
     static std::mutex mu;
     static std::map<std::pair<int, const void*>, std::pair<int, int>> cache;
@@ -3572,7 +3655,7 @@ static int run_shape(const void* kernel, int* ncu, int* per_cu) {
 // ranks sharing one device size their claims by it, whichever kernel each of them launches.
 int p_run_capacity(int vbs, int mode) {
     constexpr int NW = SO_PTILE_NW;
-    const void* ks[13];
+    const void* ks[16];
     int n = 0;
     const auto add = [&](int m, const void* k) {
         if (mode < 0 || mode == m) ks[n++] = k;
@@ -3589,6 +3672,8 @@ int p_run_capacity(int vbs, int mode) {
         add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false>));
         add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false, true>));
         add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false, false, false, true>));
+        add(kRunSingle, reinterpret_cast<const void*>(p_run_short_kernel<NW, false>));
+        add(kRunSingle, reinterpret_cast<const void*>(p_run_short_kernel<NW, true>));
         add(kRunStripe, reinterpret_cast<const void*>(p_run_kernel<NW, kRunStripe, false>));
         add(kRunFPipe, reinterpret_cast<const void*>(p_run_kernel<NW, kRunFPipe, false>));
         add(kRunTwoPass, reinterpret_cast<const void*>(p_run_kernel<NW, kRunTwoPass, false>));
@@ -3605,6 +3690,32 @@ int p_run_capacity(int vbs, int mode) {
     return best;
 }
 
+// The one-GPU plain run's tile (SO_OPT_RUN_TALL_TILES): 48 rows when forced, or when unset and
+// the frames in flight offer at least as many 48-row tiles as the tall kernel's grid has slots
+// -- below that the run is latency-bound (a frame's time is a chain of tile steps) and the
+// shorter step of the 32-row tile wins.
+static int p_run_tall_choice(int H, int W, int conc, bool zskip, bool* tall) {
+    const int opt = option(SO_OPT_RUN_TALL_TILES);
+    if (opt >= 0) {
+        *tall = opt != 0;
+        return SO_OK;
+    }
+    constexpr int NW = SO_PTILE_NW;
+    int ncu = 0, per_cu = 0;
+    const int rc = run_shape(zskip ? reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false, false, false, true>)
+                                   : reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false>),
+                             &ncu, &per_cu);
+    if (rc != SO_OK) return rc;
+    using GT = RunGeoTall<NW>;
+    *tall = (long long)run_tiles(H, W, GT::TBX, GT::TBY) * conc >= (long long)ncu * per_cu;
+    return SO_OK;
+}
+int p_run_tile_rows(int H, int W, int conc) {
+    bool tall = false;
+    if (p_run_tall_choice(H, W, conc, false, &tall) != SO_OK) return -1;
+    return tall ? RunGeoTall<SO_PTILE_NW>::TBY : Sea2Geo::TBY;
+}
+
 // refs / deps (may be null: one run, frame g predicting from g - 1 and frame 0 from ref0): frame g
 // predicts from outs[deps[g]].recon when deps[g] >= 0 (0 <= deps[g] < g), else from refs[g].
 // conc: independent runs interleaved in the list (their tiles are in flight together).
@@ -3613,7 +3724,7 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
                           const int32_t* qp_row, const PFrameOut* outs, uint32_t* ws, const PRunStripe& sp0,
                           int max_wg, hipStream_t st, const uint8_t* const* refs = nullptr,
                           const int* deps = nullptr, int conc = 1, double lam = 0.0) {
-    using G = Sea2GeoT<SO_PTILE_NW>;
+    using GS = Sea2GeoT<SO_PTILE_NW>;
     // the test-hook instantiation (one GPU only) while SO_OPT_COUNT_SAD_OPS / _TEST_LOSE_FLAG is set
     const bool hook_set = option(SO_OPT_COUNT_SAD_OPS) != 0 || option(SO_OPT_TEST_LOSE_FLAG) != 0;
     if (hook_set && MODE != kRunSingle) {   // no hook instantiation here: refuse rather than ignore
@@ -3631,7 +3742,18 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
     // when the grid has more slots than a frame has tiles
     constexpr bool VL_OK = MODE == kRunSingle && VBS;
     const bool vlat_ok = VL_OK && uqp && !hooks && SO_VBS_BALLOT_LATENCY;
+    // the plain one-GPU run without hooks: p_run_kernel on 48-row tiles or its 32-row twin
+    constexpr bool TALL_OK = MODE == kRunSingle && !VBS;
+    bool tall = false;
+    if (TALL_OK && !hooks) {
+        const int rc = p_run_tall_choice(H, W, conc, zskip, &tall);
+        if (rc != SO_OK) return rc;
+    }
+    const int tby = tall ? RunGeoTall<SO_PTILE_NW>::TBY : GS::TBY;
     const void* const kfn =
+        TALL_OK && !hooks && !tall
+            ? (zskip ? reinterpret_cast<const void*>(p_run_short_kernel<SO_PTILE_NW, true>)
+                     : reinterpret_cast<const void*>(p_run_short_kernel<SO_PTILE_NW, false>)) :
         hooks ? (uqp ? reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, MODE == kRunSingle, VBS>)
                      : reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, MODE == kRunSingle>))
               : (uqp     ? reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, false, VBS>)
@@ -3652,7 +3774,7 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
     }
     const int nbx = W / 16;
     const int rows = MODE == kRunStripe ? sp0.by1 - sp0.by0 : H / 16;
-    const long ntiles = (long)((nbx + G::TBX - 1) / G::TBX) * ((rows + G::TBY - 1) / G::TBY);
+    const long ntiles = (long)((nbx + GS::TBX - 1) / GS::TBX) * ((rows + tby - 1) / tby);
     for (int f0 = 0; f0 < nframes; f0 += kRunMax) {
         const int n = nframes - f0 < kRunMax ? nframes - f0 : kRunMax;
         PRunArgs a{};
@@ -3691,7 +3813,7 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
         sp.count_ops = option(SO_OPT_COUNT_SAD_OPS);
         sp.lose_task = f0 == 0 ? option(SO_OPT_TEST_LOSE_FLAG) : 0;
         if (MODE == kRunTwoPass || MODE == kRunFPipe2P) {   // pass 2 of a row about one grid's worth of tasks after its pass 1
-            const int tiles_x = (nbx + G::TBX - 1) / G::TBX, ntr = (rows + G::TBY - 1) / G::TBY;
+            const int tiles_x = (nbx + GS::TBX - 1) / GS::TBX, ntr = (rows + GS::TBY - 1) / GS::TBY;
             // about one grid's worth of tile rows (a pass-2 task then rarely waits holding its
             // slot), capped by the caller's lag (the frame pipeline: consecutive frames on
             // different ranks trail each other by ~lag + 2 rows, so more ranks want less)
@@ -3714,7 +3836,18 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
             SO_P_RUN_GO(false, VBS, VL_OK);
         else if (uqp)
             SO_P_RUN_GO(false, VBS, false);
-        else if (zskip)
+        else if (TALL_OK && !tall) {
+            if constexpr (TALL_OK) {
+                if (zskip)
+                    hipLaunchKernelGGL((p_run_short_kernel<SO_PTILE_NW, true>), dim3((unsigned)grid),
+                                       dim3(SO_PTILE_NW * 64), 0, st, a, n, r0, H, W, qp_rd, qp_row, ws,
+                                       (int)(f0 * ntiles), sp, lam);
+                else
+                    hipLaunchKernelGGL((p_run_short_kernel<SO_PTILE_NW, false>), dim3((unsigned)grid),
+                                       dim3(SO_PTILE_NW * 64), 0, st, a, n, r0, H, W, qp_rd, qp_row, ws,
+                                       (int)(f0 * ntiles), sp, lam);
+            }
+        } else if (zskip)
             SO_P_RUN_GO(false, false, ZS_OK);
         else
             SO_P_RUN_GO(false, false, false);

@@ -63,6 +63,8 @@ struct PRunStripe {
 
 size_t p_run_workspace_words(int H, int W);
 int p_run_capacity(int vbs, int mode = -1);
+// block rows per tile (2 or 3) of the one-GPU plain run of `conc` interleaved runs; <= 0: query failed
+int p_run_tile_rows(int H, int W, int conc);
 bool p_run_2pass_fused_ok(int H, int W);
 int32_t* p_run_t1_region(uint32_t* ws, int H, int W);
 // vbs / lam: VBSEnable (the block + sub-block search and the RD split inside the run)
