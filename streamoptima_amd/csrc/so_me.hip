@@ -2124,8 +2124,8 @@ constexpr float kFwdBound = 2.6e-7f;   // >= 2.512e-7 (above) + the rounding of 
 // product's D (lane (c4, v): Y[4 c4 + i][v]) is the second's B operand as it stands.  Writes
 // the 256 levels as int16 rows to the start of the block's scratch and flags the block in
 // S.fwd_flags when the certificate fails.
-template <class G>
-SO_DEV void fwd_mfma(PTileLds<G>& S, int g, int ln, const float (&cs)[4], int bx0, int byt0, int nbx, int by1,
+template <class G, bool HALFTQ>
+SO_DEV void fwd_mfma(PTileLds<G, false, HALFTQ>& S, int g, int ln, const float (&cs)[4], int bx0, int byt0, int nbx, int by1,
                      int qp_rd, const int32_t* __restrict__ qp_row, const int32_t* __restrict__ qp_map) {
     constexpr int SR = G::SR, TBX = G::TBX;
     const int bxl = g % TBX, byl = g / TBX;
@@ -2152,7 +2152,7 @@ SO_DEV void fwd_mfma(PTileLds<G>& S, int g, int ln, const float (&cs)[4], int bx
     for (int s = 0; s < 4; ++s) z = __builtin_amdgcn_mfma_f32_16x16x4f32(cs[s], y[s], z, 0, 0, 0);   // Z = C Y
     const float delta = __builtin_fmaf((float)sab, kFwdBound, 0x1p-20f);
     bool near = qpr < 1;
-    int16_t* qd = reinterpret_cast<int16_t*>(S.un + g * kTqScratch);
+    int16_t* qd = reinterpret_cast<int16_t*>(S.un + g * tq_scratch<G, HALFTQ>());   // tq16_exact's `scratch` of block g
 #pragma unroll
     for (int i = 0; i < 4; ++i) {   // z[i] = Z[4 c4 + i][r]
         const int u = 4 * c4 + i, k = q_exp_fast<16>(u, r, qpr);
@@ -2622,7 +2622,7 @@ SO_DEV void ptile_body(PTileLds<G, VBS, HALFTQ>& S, int tile, const uint8_t* __r
 #pragma unroll
         for (int s = 0; s < 4; ++s) cs[s] = dct16_f32(ln & 15, 4 * (ln >> 4) + s);
         for (int g = tid >> 6; g < G::NBLK; g += G::NW)
-            fwd_mfma<G>(S, g, ln, cs, bx0, byt0, nbx, by1, qp_rd, qp_row, qp_map);
+            fwd_mfma<G, HALFTQ>(S, g, ln, cs, bx0, byt0, nbx, by1, qp_rd, qp_row, qp_map);
         __syncthreads();
 #ifdef SO_FWD_COUNT   // A/B builds only: the flagged blocks replace the SAD count (words 66..67)
         if (tid == 0) S.st[2] = (uint32_t)__builtin_popcount(S.fwd_flags);
