@@ -562,6 +562,31 @@ int so_sse_u8(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* out_sse,
               void* stream);
 
 /*
+ * SSIM of nframes pairs of uint8 planes (calculate_metrics, Encoder.py:934-935:
+ * skimage.metrics.structural_similarity(a, b, win_size=win) on uint8 frames): data range 255,
+ * uniform win x win window, sample covariance, K1 0.01, K2 0.03, and the mean of S over the
+ * (H - win + 1) x (W - win + 1) windows that lie fully inside the picture (skimage crops a border
+ * of (win - 1) / 2).  With NP = win^2 and the exact integer window sums sx, sy, sxx, syy, sxy:
+ *   ux = sx / NP, uy = sy / NP, vx = (NP sxx - sx^2) / (NP (NP - 1)), vy and vxy alike,
+ *   S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),  C1 = 2.55^2, C2 = 7.65^2,
+ * evaluated in FP64.
+ *   a, b       HOST arrays of nframes device pointers; pair i is a[i] against b[i].  Planes need no
+ *              alignment; row y of a plane starts pitch bytes after row y - 1 (pitch_a / pitch_b
+ *              >= W, in bytes), so the H x W picture area of a padded plane is measured alone
+ *   win        odd, 3..15 (the reference uses 11); H >= win and W >= win
+ *   out        nframes device doubles
+ *   workspace  device doubles [so_ssim_workspace_elems(nframes, H, W, win)] (0 for a geometry
+ *              so_ssim_u8 rejects): one partial per tile, every one written before it is read
+ *              (no zeroing needed).  One workspace serves one stream at a time.
+ * A frame's partials are added in a fixed order with no floating-point atomics: its value has
+ * the same bits from run to run and whether it is computed alone or inside a batch.  Identical
+ * planes give exactly 1.0.  nframes == 0 returns SO_OK.
+ */
+size_t so_ssim_workspace_elems(int nframes, int H, int W, int win);
+int so_ssim_u8(const uint8_t* const* a, const uint8_t* const* b, int nframes, int H, int W,
+               size_t pitch_a, size_t pitch_b, int win, double* out, double* workspace, void* stream);
+
+/*
  * out[i] = sum of rows[i][0..len) (int32 -> int64) for i < n: the per-frame SSE of a GOP from
  * the encode kernels' per-block / per-row out_sse arrays (rows: a HOST array of device
  * pointers), one launch.

@@ -51,7 +51,8 @@ class Y_Video_codec(BlockAPI):
     def __init__(self, h_pixels, w_pixels, frames, block_size, search_range, Qp, intra_dur, intra_mode,
                  lam=None, VBSEnable=False, nRefFrames=1, yuv_file=None, y_only_frame_arr=None,
                  fast_me=False, FMEEnable=False, RCFlag=None, targetBR=None, frame_rate=30,
-                 qp_rate_tables=None, intra_thresh=None, ParallelMode=0, device=None, roi=None, qp_clamp=(0, 12)):
+                 qp_rate_tables=None, intra_thresh=None, ParallelMode=0, device=None, roi=None, qp_clamp=(0, 12),
+                 ssim=False):
         if fast_me and ParallelMode == 2 and VBSEnable:
             raise ValueError("fast_me + VBSEnable under ParallelMode 2: the reference raises NameError on "
                              "`mvp` (inter_prediction_parallel, Encoder.py:609)")
@@ -109,6 +110,10 @@ class Y_Video_codec(BlockAPI):
         # RCFlag 3 = two-pass RC (pass-1 token counts -> per-block QP map, so_qp_map)
         self.roi = roi
         self.qp_clamp = tuple(qp_clamp)
+        # build extension: ssim=True measures every frame's SSIM on the GPU (so_ssim_u8, the
+        # reference's skimage call with win_size 11, Encoder.py:935); off, SSIM stays NaN
+        self.ssim = bool(ssim)
+        self.ssim_per_frame = None
         self._engine = None
         self._symbols = None
 
@@ -332,7 +337,10 @@ class Y_Video_codec(BlockAPI):
         self._symbols = syms
         # closed-loop decode of the same symbols (Encoder.py:1873); result kept on device
         self.decoded_device = self.decoder.decode_symbols(syms, eng)
-        pkg = LazyPackage(self, syms, psnr_per_frame, result["frame_type"], result["qp_rows"])
+        if self.ssim:
+            self.ssim_per_frame = [float(v) for v in result["ssim"].cpu().tolist()]
+        pkg = LazyPackage(self, syms, psnr_per_frame, result["frame_type"], result["qp_rows"],
+                          ssim=self.ssim_per_frame if self.ssim else None)
         if any("qp_map" in s.extra for s in syms):
             pkg["QP map per frame"] = [s.extra["qp_map"].cpu().numpy() if "qp_map" in s.extra else None for s in syms]
         self.encoded_package_f = True
@@ -348,7 +356,9 @@ class Y_Video_codec(BlockAPI):
         a device SSE array.  check=True ends with one host read of the persistent runs'
         timeout count (Engine.check_run: raises if a dependency wait timed out); a caller
         that times back-to-back GOPs passes False and calls engine().check_run() after them.
-        Otherwise no host sync unless RCFlag > 1 needs residual_size.
+        Otherwise no host sync unless RCFlag > 1 needs residual_size.  With ssim=True the
+        result also holds "ssim", a device float64 [F]: every input frame against its
+        reconstruction over the h_pixels x w_pixels picture area (Engine.ssim, one call).
 
         Streaming hooks (hoststream.HostStreamEncoder): a persistent P-run covers at most
         `chunk` frames per launch; wait_input(k0, k1) is called before the work reading frames
@@ -483,7 +493,15 @@ class Y_Video_codec(BlockAPI):
         sse = eng.sum_rows([s.sse for s in out_syms])
         if check and (pipelined or pipelined2):
             eng.check_run()
-        return {"symbols": out_syms, "sse": sse, "frame_type": ftypes, "qp_rows": qp_rows}
+        res = {"symbols": out_syms, "sse": sse, "frame_type": ftypes, "qp_rows": qp_rows}
+        if self.ssim:
+            res["ssim"] = self._ssim_device(eng, frames_dev, out_syms)
+        return res
+
+    def _ssim_device(self, eng, frames_dev, syms) -> torch.Tensor:
+        """SSIM of every frame of a GOP against its reconstruction, picture area only."""
+        return eng.ssim([frames_dev[i] for i in range(len(syms))], [s.recon for s in syms], self.h_pixels,
+                        self.w_pixels)
 
     def encode_gops_device(self, gops: list, intra_dur: int, symbols=None, check: bool = True) -> list:
         """Several GOPs (device-resident [F, Hp, Wp] each, e.g. consecutive GOPs of one stream
@@ -525,10 +543,12 @@ class Y_Video_codec(BlockAPI):
         if rc_on:   # the state encode_device leaves (each frame ends on its last row's QP)
             self.set_Qp(qp_sched[-1])
         res = []
-        for syms in outs:
+        for frames_dev, syms in zip(gops, outs):
             res.append({"symbols": syms, "sse": eng.sum_rows([s.sse for s in syms]),
                         "frame_type": [s.frame_type for s in syms],
                         "qp_rows": [list(qp_sched) if rc_on else [] for _ in syms]})
+            if self.ssim:
+                res[-1]["ssim"] = self._ssim_device(eng, frames_dev, syms)
         if check:
             eng.check_run()
         return res

@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import Engine, alloc_planes
+from .engine import Engine, alloc_planes, ssim_planes
 from .package import frame_mvs, symbols_to_host
 
 
@@ -132,25 +132,44 @@ class BlockAPI:
     # ---- metrics (Encoder.py:934-935) -----------------------------------------------------------
     def calculate_metrics(self, original_frame, modified_frame):
         """(PSNR with data_range 255, SSIM).  PSNR = 10 log10(255^2 / MSE) from the device SSE
-        (so_sse_u8); SSIM is out of scope (skimage is absent): NaN."""
+        (so_sse_u8).  SSIM is NaN unless the codec was built with ssim=True: then it is
+        structural_similarity(a, b, win_size=11) of two 2-D frames holding integer values in
+        [0, 255], measured on the GPU (so_ssim_u8); like skimage, a side shorter than the
+        window raises ValueError."""
         a, b = np.asarray(original_frame), np.asarray(modified_frame)
         if a.shape != b.shape:
             raise ValueError(f"shapes differ: {a.shape} vs {b.shape}")
         n = a.size
+        want_ssim = bool(getattr(self, "ssim", False))
+        if want_ssim and (a.ndim != 2 or min(a.shape) < 11):
+            raise ValueError(f"SSIM: win_size 11 exceeds a side of the {a.shape} frames (2-D frames of 11 pixels "
+                             "or more per side)")
+        ssim = float("nan")
         if all(x.dtype == np.uint8 or (np.all(x == np.round(x)) and x.min() >= 0 and x.max() <= 255) for x in (a, b)):
             lib = _lib.load()
             pa, pb = _u8_plane(a.reshape(a.shape[0], -1), self.device), _u8_plane(b.reshape(b.shape[0], -1), self.device)
             acc = torch.zeros(1, dtype=torch.int64, device=self.device)
             _lib.check(lib.so_sse_u8(pa.data_ptr(), pb.data_ptr(), n, acc.data_ptr(), _lib.stream_handle(self.device)),
                        "so_sse_u8")
+            if want_ssim:
+                h, w = a.shape
+                need = lib.so_ssim_workspace_elems(1, h, w, 11)
+                ws = self.__dict__.get("_ssim_ws")
+                if ws is None or ws.numel() < need:
+                    ws = self.__dict__["_ssim_ws"] = torch.empty(need, dtype=torch.float64, device=self.device)
+                ssim_dev = ssim_planes(lib, self.device, [pa], [pb], h, w, 11, None, ws)
             sse = float(acc.item())
+            if want_ssim:
+                ssim = float(ssim_dev.item())
         else:
+            if want_ssim:
+                raise ValueError("SSIM: frames must hold integer pixel values in [0, 255]")
             ta = torch.from_numpy(a.astype(np.float64)).to(self.device)
             tb = torch.from_numpy(b.astype(np.float64)).to(self.device)
             sse = float(((ta - tb) ** 2).sum().item())
         mse = sse / n
         psnr = float("inf") if mse == 0 else float(10 * np.log10((255 ** 2) / mse))
-        return psnr, float("nan")
+        return psnr, ssim
 
     # ---- FME frac frame (Encoder.py:388-403) ----------------------------------------------------
     def frac_me_reference_frame(self, ref_frames, block_size=None):

@@ -76,6 +76,9 @@ int stripe_halo_push_launch(const uint8_t* plane, int W, int by0, int by1, uint8
                             uint32_t* up_flags, uint32_t* dn_flags, int gf, uint32_t epoch, hipStream_t st);
 int frame_push_launch(const uint8_t* plane, int H, int W, uint8_t* dst, uint32_t* flags, uint32_t epoch,
                       hipStream_t st);
+size_t ssim_tiles(int H, int W, int win);   // so_ssim.hip
+int ssim_launch(const uint8_t* const* a, const uint8_t* const* b, int nframes, int H, int W, size_t pitch_a,
+                size_t pitch_b, int win, double* out, double* ws, hipStream_t st);
 
 #ifdef SO_AB
 // A/B builds only (not in the header): tools that set the SO_AB environment knobs
@@ -1166,6 +1169,43 @@ int so_sse_u8(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* out_sse, 
     hipLaunchKernelGGL(sse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, n,
                        reinterpret_cast<unsigned long long*>(out_sse));
     return check_launch("sse_kernel");
+}
+
+// ---- SSIM (so_ssim.hip) -----------------------------------------------------------------------
+size_t so_ssim_workspace_elems(int nframes, int H, int W, int win) {
+    if (nframes <= 0 || (long long)H * W > (1ll << 31)) return 0;
+    return (size_t)nframes * ssim_tiles(H, W, win);
+}
+
+int so_ssim_u8(const uint8_t* const* a, const uint8_t* const* b, int nframes, int H, int W, size_t pitch_a,
+               size_t pitch_b, int win, double* out, double* workspace, void* stream) {
+    const char* fn = "so_ssim_u8";
+    if (win < 3 || win > 15 || win % 2 == 0) {
+        set_error("%s: win %d (odd, 3..15)", fn, win);
+        return SO_E_INVALID;
+    }
+    if (H < win || W < win) {
+        set_error("%s: picture %dx%d is smaller than the %d-pixel window", fn, W, H, win);
+        return SO_E_INVALID;
+    }
+    if ((long long)H * W > (1ll << 31)) {
+        set_error("%s: frame too large", fn);
+        return SO_E_INVALID;
+    }
+    if (pitch_a < (size_t)W || pitch_b < (size_t)W) {
+        set_error("%s: pitch %zu / %zu below the width %d", fn, pitch_a, pitch_b, W);
+        return SO_E_INVALID;
+    }
+    if (nframes < 0) {
+        set_error("%s: nframes %d", fn, nframes);
+        return SO_E_INVALID;
+    }
+    if (nframes == 0) return SO_OK;
+    SO_NEED(a, fn); SO_NEED(b, fn); SO_NEED(out, fn); SO_NEED(workspace, fn);
+    for (int i = 0; i < nframes; ++i) {
+        SO_NEED(a[i], fn); SO_NEED(b[i], fn);
+    }
+    return ssim_launch(a, b, nframes, H, W, pitch_a, pitch_b, win, out, workspace, (hipStream_t)stream);
 }
 
 // ---- packed symbol stream (so_pack.hip) -----------------------------------------------------

@@ -34,6 +34,34 @@ def alloc_planes(n: int, h: int, w: int, device, fill: int | None = None) -> tor
     return flat[: n * h * w].view(n, h, w)
 
 
+def ssim_planes(lib, device, a_planes, b_planes, h: int, w: int, win: int, out, ws: torch.Tensor) -> torch.Tensor:
+    """so_ssim_u8 over pairs of uint8 planes (2-D tensors with contiguous rows, one row stride
+    per side) into `out` (float64 [n], allocated when None); `ws` is the float64 workspace."""
+    a_planes, b_planes = list(a_planes), list(b_planes)
+    n = len(a_planes)
+    if len(b_planes) != n:
+        raise ValueError(f"ssim: {n} planes against {len(b_planes)}")
+    out = torch.empty(n, dtype=torch.float64, device=device) if out is None else out
+    if out.dtype != torch.float64 or out.numel() != n or not out.is_contiguous() or out.device != ws.device:
+        raise ValueError(f"ssim: out must be a contiguous float64 [{n}] tensor on {ws.device}")
+    if n == 0:
+        return out
+    pitches = []
+    for name, planes in (("a", a_planes), ("b", b_planes)):
+        for t in planes:
+            if (t.dtype != torch.uint8 or t.dim() != 2 or t.device != ws.device or t.shape[0] < h or t.shape[1] < w
+                    or t.stride(1) != 1 or t.stride(0) != planes[0].stride(0)):
+                raise ValueError(f"ssim: {name} planes must be uint8 2-D tensors of at least {h}x{w} on {ws.device} "
+                                 "with contiguous rows and one row stride")
+        pitches.append(int(planes[0].stride(0)))
+    pa = (ctypes.c_void_p * n)(*[t.data_ptr() for t in a_planes])
+    pb = (ctypes.c_void_p * n)(*[t.data_ptr() for t in b_planes])
+    rc = lib.so_ssim_u8(pa, pb, n, int(h), int(w), pitches[0], pitches[1], int(win), out.data_ptr(), ws.data_ptr(),
+                        _lib.stream_handle(device))
+    _lib.check(rc, "so_ssim_u8")
+    return out
+
+
 @dataclass
 class FrameSymbols:
     """Per-frame output of the encode path (canonical layout, include/streamoptima.h)."""
@@ -533,6 +561,19 @@ class Engine:
         rc = self.lib.so_sum_i32_rows(ptrs, n, length, out.data_ptr(), _lib.stream_handle(self.device))
         _lib.check(rc, "so_sum_i32_rows")
         return out
+
+    def ssim(self, a_planes, b_planes, h: int, w: int, win: int = 11, out: torch.Tensor | None = None) -> torch.Tensor:
+        """float64 [n] on the device: the SSIM (uniform win x win window, as the reference's
+        skimage call) of a_planes[i] against b_planes[i] over their top-left h x w pixels, one
+        batched so_ssim_u8 call, no host synchronisation.  The planes are uint8 2-D tensors
+        (or [n, H, W] stacks) whose rows are contiguous; a padded plane is measured over its
+        picture area through its row stride.  The workspace is cached on the engine."""
+        n = len(a_planes)
+        need = self.lib.so_ssim_workspace_elems(n, h, w, win)
+        ws = getattr(self, "_ssim_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._ssim_ws = torch.empty(max(need, 1), dtype=torch.float64, device=self.device)
+        return ssim_planes(self.lib, self.device, a_planes, b_planes, h, w, win, out, ws)
 
     def sse_into(self, a: torch.Tensor, b: torch.Tensor, acc: torch.Tensor) -> None:
         """acc (uint64 view of an int64 device scalar) += sum((a-b)^2)."""

@@ -60,7 +60,7 @@ class LazyPackage(dict):
 
     _LAZY = ("MVS per Frame", "approx residual", "MAE per Frame")
 
-    def __init__(self, codec, symbols, psnr, frame_types, qp_rows):
+    def __init__(self, codec, symbols, psnr, frame_types, qp_rows, ssim=None):
         super().__init__()
         self._codec = codec
         self._symbols = symbols
@@ -71,7 +71,8 @@ class LazyPackage(dict):
         self["width in pixels"] = codec.w_pixels
         self["search range"] = codec.search_range
         self["PSNR per frame"] = psnr
-        self["SSIM per frame"] = [float("nan")] * len(psnr)   # skimage SSIM is out of scope
+        # measured on the GPU when the codec was built with ssim=True (so_ssim_u8), NaN otherwise
+        self["SSIM per frame"] = list(ssim) if ssim is not None else [float("nan")] * len(psnr)
         self["Qp_per_row_per_frame"] = qp_rows
         self["frame_type_seq"] = list(frame_types)
 
