@@ -587,6 +587,46 @@ int so_ssim_u8(const uint8_t* const* a, const uint8_t* const* b, int nframes, in
                size_t pitch_a, size_t pitch_b, int win, double* out, double* workspace, void* stream);
 
 /*
+ * Chroma 4:2:0 (build extension: the reference codes luma only; DESIGN.md "Chroma 4:2:0").  U and V
+ * of one frame, encoded from the LUMA frame's motion: luma block b = (bx, by) of the 16x16 grid
+ * owns the 8x8 block at (8 bx, 8 by) of each chroma plane (H/2 x W/2, pitch W/2; H, W: the padded
+ * luma size), one launch for both planes, asynchronous on `stream`.
+ *   prediction   frame_type 0: every sample 128.  frame_type 1: the block's luma MV mv[b][0] =
+ *                (dx, dy, r) -- mv[b][j] for its 4x4 quadrant j (Z order) when split[b] -- in
+ *                half-sample units: ix = dx >> 1, fx = dx & 1, x0 = clamp(X + ix, 0, W/2 - 1),
+ *                x1 = clamp(X + ix + fx, 0, W/2 - 1), y alike,
+ *                P = (R[y0][x0] + R[y0][x1] + R[y1][x0] + R[y1][x1] + 2) >> 2 on the chroma plane R
+ *                of reference clamp(r, 0, nref - 1): total for any MV, exact integers
+ *   transform    one 8x8 per block, the reference's per-block functions at N = 8: apply_2d_dct
+ *                (Encoder.py:779), quantize_TC with generate_Q_matrix(8, qpc) (:787, :938),
+ *                len(entropy_encoder_block) (:1086), rescale_QTC, apply_2d_idct (:810),
+ *                (P + idct).astype(uint8) (:824, mod-256 wrap)
+ *   qpc          clamp(base + qp_offset, 0, 20), base = qp_map[b] if qp_map, else qp_row[by] if
+ *                qp_row, else qp -- the values the luma frame was given (no -1 for split blocks)
+ *   cur_u/v      the frame's chroma planes;  refs_u/v: HOST arrays of nref device pointers, the
+ *                chroma reconstructions in the luma reference list's order (frame_type 1 only;
+ *                ignored, with nref, for frame_type 0, as are split and mv)
+ *   split, mv    the luma frame's symbols (uint8 [nb], int16 [nb][4][3])
+ *   out_qtc_u/v  int16 [nb][64] row-major;  out_tokens, out_sse: int32 [2][nb] (U then V), the
+ *                token count and the sum of (cur - recon)^2 of every block
+ * Planes must be 8-byte aligned and qtc arrays 16-byte aligned; nothing outside a plane is read.
+ * bs != 16 is SO_E_UNSUPPORTED; H or W not a multiple of 16, a frame_type other than 0 / 1, nref
+ * outside 1..SO_MAX_REF on a P-frame, a NULL required pointer or a reconstruction that aliases a
+ * reference (or the other reconstruction) is SO_E_INVALID, before any launch.
+ * so_chroma_recon_frame is the decoder: the same prediction and inverse path from qtc_u / qtc_v.
+ */
+int so_chroma_encode_frame(const uint8_t* cur_u, const uint8_t* cur_v, const uint8_t* const* refs_u,
+                           const uint8_t* const* refs_v, int nref, int H, int W, int bs, int frame_type,
+                           const uint8_t* split, const int16_t* mv, int qp, const int32_t* qp_row,
+                           const int32_t* qp_map, int qp_offset, int16_t* out_qtc_u, int16_t* out_qtc_v,
+                           int32_t* out_tokens, uint8_t* out_recon_u, uint8_t* out_recon_v, int32_t* out_sse,
+                           void* stream);
+int so_chroma_recon_frame(const uint8_t* const* refs_u, const uint8_t* const* refs_v, int nref, int H, int W,
+                          int bs, int frame_type, const uint8_t* split, const int16_t* mv, int qp,
+                          const int32_t* qp_row, const int32_t* qp_map, int qp_offset, const int16_t* qtc_u,
+                          const int16_t* qtc_v, uint8_t* out_recon_u, uint8_t* out_recon_v, void* stream);
+
+/*
  * out[i] = sum of rows[i][0..len) (int32 -> int64) for i < n: the per-frame SSE of a GOP from
  * the encode kernels' per-block / per-row out_sse arrays (rows: a HOST array of device
  * pointers), one launch.

@@ -52,7 +52,13 @@ class Y_Video_codec(BlockAPI):
                  lam=None, VBSEnable=False, nRefFrames=1, yuv_file=None, y_only_frame_arr=None,
                  fast_me=False, FMEEnable=False, RCFlag=None, targetBR=None, frame_rate=30,
                  qp_rate_tables=None, intra_thresh=None, ParallelMode=0, device=None, roi=None, qp_clamp=(0, 12),
-                 ssim=False):
+                 ssim=False, chroma=False, chroma_qp_offset=0, uv_frame_arr=None):
+        if chroma and FMEEnable:
+            raise NotImplementedError("chroma with FMEEnable is not built: the luma MVs are in half-pel units there")
+        if chroma and block_size != 16:
+            raise NotImplementedError(f"chroma needs block_size 16 (8x8 chroma blocks), got {block_size}")
+        if chroma and (h_pixels % 2 or w_pixels % 2):
+            raise ValueError(f"chroma 4:2:0 needs an even picture size, got {w_pixels}x{h_pixels}")
         if fast_me and ParallelMode == 2 and VBSEnable:
             raise ValueError("fast_me + VBSEnable under ParallelMode 2: the reference raises NameError on "
                              "`mvp` (inter_prediction_parallel, Encoder.py:609)")
@@ -114,6 +120,25 @@ class Y_Video_codec(BlockAPI):
         # reference's skimage call with win_size 11, Encoder.py:935); off, SSIM stays NaN
         self.ssim = bool(ssim)
         self.ssim_per_frame = None
+        # build extension (DESIGN.md "Chroma 4:2:0"): chroma=True also codes U and V from the luma
+        # frame's motion (so_chroma_encode_frame); uv_frame_arr: [F, 2, h/2, w/2] uint8, or the
+        # planes of yuv_file.  Off (default) nothing is allocated and no launch is added.
+        self.chroma = bool(chroma)
+        self.chroma_qp_offset = int(chroma_qp_offset)
+        self.uv_f_arr = None
+        if self.chroma:
+            if yuv_file is not None and uv_frame_arr is None:
+                _, u, v = self.read_yuv420_planes(yuv_file, h_pixels, w_pixels, frames)
+                uv_frame_arr = np.stack([u, v], axis=1)
+            if uv_frame_arr is not None:
+                uv_frame_arr = np.asarray(uv_frame_arr)
+                if uv_frame_arr.ndim != 4 or tuple(uv_frame_arr.shape[1:]) != (2, h_pixels // 2, w_pixels // 2):
+                    raise ValueError(f"uv_frame_arr must be [F, 2, {h_pixels // 2}, {w_pixels // 2}], got "
+                                     f"{tuple(uv_frame_arr.shape)}")
+            self.uv_f_arr = uv_frame_arr
+        self.chroma_symbols = None
+        self.psnr_per_frame_u = self.psnr_per_frame_v = None
+        self.decoded_chroma_device = None
         self._engine = None
         self._symbols = None
 
@@ -146,6 +171,20 @@ class Y_Video_codec(BlockAPI):
                 out[i] = np.frombuffer(f.read(size_y), dtype=np.uint8).reshape(height, width)
                 f.read(size_uv * 2)
         return out
+
+    @staticmethod
+    def read_yuv420_planes(raw_yuv_420_f, height, width, frames):
+        """(Y [F, H, W], U, V [F, H/2, W/2]) uint8 of a planar 4:2:0 file (Y | U | V per frame)."""
+        if height % 2 or width % 2:
+            raise ValueError(f"4:2:0 needs an even picture size, got {width}x{height}")
+        size_y, hc, wc = width * height, height // 2, width // 2
+        raw = np.fromfile(raw_yuv_420_f, dtype=np.uint8, count=frames * (size_y + 2 * hc * wc))
+        if raw.size != frames * (size_y + 2 * hc * wc):
+            raise ValueError(f"{raw_yuv_420_f}: shorter than {frames} frames of {width}x{height} 4:2:0")
+        raw = raw.reshape(frames, size_y + 2 * hc * wc)
+        return (raw[:, :size_y].reshape(frames, height, width).copy(),
+                raw[:, size_y:size_y + hc * wc].reshape(frames, hc, wc).copy(),
+                raw[:, size_y + hc * wc:].reshape(frames, hc, wc).copy())
 
     def pad_hw(self, array, i, pad_with=None):
         """Encoder.py:140-155: pad to a multiple of i (float64, like the reference)."""
@@ -248,6 +287,47 @@ class Y_Video_codec(BlockAPI):
             planes.copy_(src)
         return planes
 
+    def _upload_uv_padded(self, arr) -> torch.Tensor:
+        """host chroma planes [F, 2, h/2, w/2] -> [F, 2, Hp/2, Wp/2] uint8 in HBM (padded with 128)."""
+        a = np.asarray(arr)
+        hp, wp = self._geometry()
+        f, _, h, w = a.shape
+        planes = alloc_planes(f * 2, hp // 2, wp // 2, self.device).view(f, 2, hp // 2, wp // 2)
+        src = torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8, copy=False)))
+        if (h, w) != (hp // 2, wp // 2):
+            planes.fill_(128)
+            planes[:, :, :h, :w].copy_(src, non_blocking=False)
+        else:
+            planes.copy_(src)
+        return planes
+
+    def _encode_chroma_gop(self, eng, uv_dev, syms) -> dict:
+        """U and V of every frame of a GOP from its luma symbols: a stream-ordered chain of one
+        launch per frame behind the luma work (a P-frame's chroma reads the chroma reconstruction
+        of its references).  The reference list is the luma one's: one all-128 plane at first, an
+        I-frame clears it, every reconstruction is appended, the oldest dropped at nRefFrames."""
+        n = len(syms)
+        if uv_dev is None or tuple(uv_dev.shape) != (n, 2, eng.h // 2, eng.w // 2) or uv_dev.dtype != torch.uint8:
+            raise ValueError(f"chroma=True needs uv planes [{n}, 2, {eng.h // 2}, {eng.w // 2}] uint8 on the device")
+        if getattr(eng, "_cref128", None) is None:
+            eng._cref128 = alloc_planes(1, eng.h // 2, eng.w // 2, self.device, fill=128)[0]
+        refs_u, refs_v = [eng._cref128], [eng._cref128]
+        out = []
+        for i, s in enumerate(syms):
+            if s.frame_type == 0:
+                refs_u, refs_v = [], []
+            c = eng.encode_chroma(s, uv_dev[i, 0], uv_dev[i, 1], refs_u, refs_v, self.chroma_qp_offset)
+            out.append(c)
+            if i < n - 1:
+                if len(refs_u) >= self.nRefFrames:
+                    refs_u.pop(0)
+                    refs_v.pop(0)
+                refs_u.append(c.recon_u)
+                refs_v.append(c.recon_v)
+        # per frame: SSE of U, SSE of V, tokens of U, tokens of V -- one reduction per GOP
+        sums = eng.sum_rows([r for c in out for r in (c.sse[0], c.sse[1], c.tokens[0], c.tokens[1])]).view(n, 4)
+        return {"chroma_symbols": out, "chroma_sums": sums}
+
     def _rc_on(self):
         return self.RCFlag is not None and self.RCFlag > 0
 
@@ -328,7 +408,12 @@ class Y_Video_codec(BlockAPI):
         t0 = time.time()
         eng = self.engine()
         frames_dev = self._upload_padded(self.y_only_f_arr[: self.frames])
-        result = self.encode_device(frames_dev, intra_dur)
+        uv_dev = None
+        if self.chroma:
+            if self.uv_f_arr is None:
+                raise ValueError("chroma=True needs uv_frame_arr or a yuv_file")
+            uv_dev = self._upload_uv_padded(self.uv_f_arr[: self.frames])
+        result = self.encode_device(frames_dev, intra_dur, uv_dev=uv_dev)
         torch.cuda.synchronize(self.device)
         sse = result["sse"].cpu().numpy().astype(np.int64)
         hp, wp = eng.h, eng.w
@@ -336,13 +421,22 @@ class Y_Video_codec(BlockAPI):
         syms = result["symbols"]
         self._symbols = syms
         # closed-loop decode of the same symbols (Encoder.py:1873); result kept on device
-        self.decoded_device = self.decoder.decode_symbols(syms, eng)
+        self.chroma_symbols = result.get("chroma_symbols")
+        self.decoded_device = self.decoder.decode_symbols(syms, eng, chroma_symbols=self.chroma_symbols)
+        self.decoded_chroma_device = self.decoder.decoded_chroma_device if self.chroma else None
         if self.ssim:
             self.ssim_per_frame = [float(v) for v in result["ssim"].cpu().tolist()]
         pkg = LazyPackage(self, syms, psnr_per_frame, result["frame_type"], result["qp_rows"],
                           ssim=self.ssim_per_frame if self.ssim else None)
         if any("qp_map" in s.extra for s in syms):
             pkg["QP map per frame"] = [s.extra["qp_map"].cpu().numpy() if "qp_map" in s.extra else None for s in syms]
+        if self.chroma:
+            sums = result["chroma_sums"].cpu().numpy().astype(np.int64)
+            npx = (hp // 2) * (wp // 2)
+            self.psnr_per_frame_u = [_psnr_from_sse(int(r[0]), npx) for r in sums]
+            self.psnr_per_frame_v = [_psnr_from_sse(int(r[1]), npx) for r in sums]
+            pkg.add_chroma(self.chroma_symbols, self.psnr_per_frame_u, self.psnr_per_frame_v,
+                           [[int(r[2]), int(r[3])] for r in sums], self.chroma_qp_offset)
         self.encoded_package_f = True
         if save_enc_pkg:
             self.encoded_package = pkg
@@ -351,7 +445,7 @@ class Y_Video_codec(BlockAPI):
         return psnr_per_frame
 
     def encode_device(self, frames_dev: torch.Tensor, intra_dur: int, symbols=None, check: bool = True,
-                      chunk: int | None = None, wait_input=None, on_output=None):
+                      chunk: int | None = None, wait_input=None, on_output=None, uv_dev: torch.Tensor | None = None):
         """The GOP loop on device-resident frames [F, Hp, Wp].  Returns symbols per frame and
         a device SSE array.  check=True ends with one host read of the persistent runs'
         timeout count (Engine.check_run: raises if a dependency wait timed out); a caller
@@ -363,7 +457,14 @@ class Y_Video_codec(BlockAPI):
         Streaming hooks (hoststream.HostStreamEncoder): a persistent P-run covers at most
         `chunk` frames per launch; wait_input(k0, k1) is called before the work reading frames
         [k0, k1) is enqueued (to make the stream wait for their upload) and on_output(k0, k1,
-        syms) after the work producing their symbols is enqueued.  Symbols are identical."""
+        syms) after the work producing their symbols is enqueued.  Symbols are identical.
+
+        With chroma=True, uv_dev holds the frames' chroma planes [F, 2, Hp/2, Wp/2] (uint8, padded
+        with 128) and the result also holds "chroma_symbols" (a ChromaSymbols per frame) and
+        "chroma_sums" (device int64 [F, 4]: SSE of U, SSE of V, tokens of U, tokens of V), enqueued
+        after the GOP's luma work with no host synchronisation.  Luma is untouched by it."""
+        if self.chroma and (wait_input is not None or on_output is not None or chunk is not None):
+            raise NotImplementedError("chroma in the streaming encoder is not built")
         wait_input_default, on_output_default = wait_input is None, on_output is None
         wait_input = wait_input or (lambda k0, k1: None)
         on_output = on_output or (lambda k0, k1, syms: None)
@@ -426,7 +527,7 @@ class Y_Video_codec(BlockAPI):
         if pipelined and chunk is None and intra_dur < nframes - 1 and wait_input_default and on_output_default:
             # several P-runs between I-frames: independent chains, interleaved in one launch
             return self.encode_gops_device([frames_dev], intra_dur, symbols=[symbols] if symbols else None,
-                                           check=check)[0]
+                                           check=check, uv_gops=[uv_dev] if self.chroma else None)[0]
         i = 0
         while i < nframes:
             if (pipelined or pipelined2) and i % intra_dur != 0:
@@ -496,6 +597,8 @@ class Y_Video_codec(BlockAPI):
         res = {"symbols": out_syms, "sse": sse, "frame_type": ftypes, "qp_rows": qp_rows}
         if self.ssim:
             res["ssim"] = self._ssim_device(eng, frames_dev, out_syms)
+        if self.chroma:
+            res.update(self._encode_chroma_gop(eng, uv_dev, out_syms))
         return res
 
     def _ssim_device(self, eng, frames_dev, syms) -> torch.Tensor:
@@ -503,7 +606,8 @@ class Y_Video_codec(BlockAPI):
         return eng.ssim([frames_dev[i] for i in range(len(syms))], [s.recon for s in syms], self.h_pixels,
                         self.w_pixels)
 
-    def encode_gops_device(self, gops: list, intra_dur: int, symbols=None, check: bool = True) -> list:
+    def encode_gops_device(self, gops: list, intra_dur: int, symbols=None, check: bool = True,
+                           uv_gops: list | None = None) -> list:
         """Several GOPs (device-resident [F, Hp, Wp] each, e.g. consecutive GOPs of one stream
         or GOPs of different streams) encoded together: every I-frame first (they depend on
         nothing), then the P-frame runs of ALL the GOPs interleaved in one persistent launch
@@ -513,8 +617,11 @@ class Y_Video_codec(BlockAPI):
         to encode_device of that GOP alone (the reference's encode() loop, Encoder.py:1839-1867,
         once per GOP).  Covers the persistent-run configuration (no two-pass RC / ROI / RCFlag>1
         P->I switch, nRefFrames 1); returns one encode_device-style dict per GOP.
-        symbols: optional per-GOP lists of preallocated FrameSymbols to reuse."""
+        symbols: optional per-GOP lists of preallocated FrameSymbols to reuse.
+        uv_gops (chroma=True): per GOP the chroma planes [F, 2, Hp/2, Wp/2], as encode_device."""
         eng = self.engine()
+        if self.chroma and (uv_gops is None or len(uv_gops) != len(gops)):
+            raise ValueError("chroma=True needs uv_gops, one [F, 2, Hp/2, Wp/2] tensor per GOP")
         rc_switch = self.RCFlag is not None and self.RCFlag > 1 and (self.RCFlag == 2 or self.intra_thresh is not None)
         if not (eng.pipelined_ok(1) and self.nRefFrames == 1 and not rc_switch and self.roi_block_offsets() is None
                 and not (self.RCFlag is not None and self.RCFlag >= 3)):
@@ -543,12 +650,14 @@ class Y_Video_codec(BlockAPI):
         if rc_on:   # the state encode_device leaves (each frame ends on its last row's QP)
             self.set_Qp(qp_sched[-1])
         res = []
-        for frames_dev, syms in zip(gops, outs):
+        for g, (frames_dev, syms) in enumerate(zip(gops, outs)):
             res.append({"symbols": syms, "sse": eng.sum_rows([s.sse for s in syms]),
                         "frame_type": [s.frame_type for s in syms],
                         "qp_rows": [list(qp_sched) if rc_on else [] for _ in syms]})
             if self.ssim:
                 res[-1]["ssim"] = self._ssim_device(eng, frames_dev, syms)
+            if self.chroma:
+                res[-1].update(self._encode_chroma_gop(eng, uv_gops[g], syms))
         if check:
             eng.check_run()
         return res
@@ -560,6 +669,18 @@ class Y_Video_codec(BlockAPI):
         with open(self.recon_yuv_path, "wb") as f:
             for s in syms:
                 f.write(s.recon.cpu().numpy()[: self.h_pixels, : self.w_pixels].tobytes())
+
+    def save_yuv420(self, filename):
+        """The encoder's reconstruction as a planar 4:2:0 file (Y | U | V per frame), cropped to
+        the picture size.  Needs chroma=True and a finished encode()."""
+        if not self.chroma or self._symbols is None or self.chroma_symbols is None:
+            raise ValueError("save_yuv420 needs chroma=True and encode() first")
+        h, w = self.h_pixels, self.w_pixels
+        with open(filename, "wb") as f:
+            for s, c in zip(self._symbols, self.chroma_symbols):
+                f.write(s.recon.cpu().numpy()[:h, :w].tobytes())
+                f.write(c.recon_u.cpu().numpy()[: h // 2, : w // 2].tobytes())
+                f.write(c.recon_v.cpu().numpy()[: h // 2, : w // 2].tobytes())
 
     def save_y_only(self, filename, y_data_list):
         with open(filename, "wb") as f:
@@ -574,6 +695,9 @@ class Y_Video_codec(BlockAPI):
         MVs / RLE token lists packed on the GPU by so_pack_frames, ~2.4x smaller than the
         int16 QTC and far smaller than the text lines).  decoder.decode_packed_file reads it.
         Returns the file size in bytes."""
+        if self.chroma:
+            raise NotImplementedError("the packed container carries luma only: chroma is not built there "
+                                      "(use transmit_bitstream with chroma_residual_file)")
         if not self.encoded_package_f or self._symbols is None:
             print("[ERROR] No encoded package available, please run encode() first")
             return 0
@@ -581,11 +705,13 @@ class Y_Video_codec(BlockAPI):
         return packedfile.write(path, self.engine(), self._symbols, self.encoded_package["Qp_per_row_per_frame"])
 
     def transmit_bitstream(self, intra_dur=None, block_size=None, mv_file=None, residual_file=None,
-                           qp_map_file=None):
+                           qp_map_file=None, chroma_residual_file=None):
         """Encoder.py:1544-1573, writing the differential MV/QP lines and the RLE residual
         lines (entropy_encoder_frame) — the reference writes str(residuals) instead, which
         its own parser cannot read.  With ROI / two-pass RC (build extension)
-        `qp_map_file` receives one line per frame of per-block QP deltas against the row QP."""
+        `qp_map_file` receives one line per frame of per-block QP deltas against the row QP.
+        With chroma=True `chroma_residual_file` receives one line per frame: U's
+        entropy_encoder_frame line at block size 8, then '|', then V's."""
         if not self.encoded_package_f:
             print("[ERROR] No encoded package available, please run encode() first")
             return
@@ -596,6 +722,13 @@ class Y_Video_codec(BlockAPI):
                 fm.write(str(ft) + "|" + self.differential_encoder_frame(ft, pkg["MVS per Frame"][i],
                                                                          pkg["Qp_per_row_per_frame"][i]) + "\n")
                 fr.write(self.entropy_encoder_frame(pkg["approx residual"][i], block_size or self.block_size) + "\n")
+        if chroma_residual_file is not None:
+            if not self.chroma:
+                raise ValueError("chroma_residual_file needs chroma=True")
+            from .bitstream import chroma_residual_line
+            with open(chroma_residual_file, "w") as fc:
+                for u, v in pkg["chroma approx residual"]:
+                    fc.write(chroma_residual_line(u, v) + "\n")
         if qp_map_file is not None:
             from .bitstream import qp_map_line
             maps = pkg["QP map per frame"] if "QP map per frame" in pkg else None

@@ -59,6 +59,9 @@ _SIGS = {
     "so_sse_u8": ([_vp, _vp, ctypes.c_int64, _vp, _vp], _i),
     "so_ssim_workspace_elems": ([_i, _i, _i, _i], _sz),
     "so_ssim_u8": ([_vp, _vp, _i, _i, _i, _sz, _sz, _i, _vp, _vp, _vp], _i),
+    "so_chroma_encode_frame": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp], _i),
+    "so_chroma_recon_frame": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "so_block_xform": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "so_encode_p_run_stripe": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_uint32, _i, _vp], _i),

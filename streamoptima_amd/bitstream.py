@@ -277,6 +277,29 @@ def unpack_frame(buf, nb: int, bs: int, frame_type: int) -> dict:
     return {"split": split, "mv": mv, "qtc": qtc}
 
 
+# ---- chroma residual line (build extension: chroma 4:2:0) ------------------------------------------
+def chroma_residual_line(u_blocks, v_blocks) -> str:
+    """One frame's chroma coefficients: U's entropy_encoder_frame line at block size 8, '|', V's
+    (every chroma block is unsplit: one 8x8 transform per 16x16 luma block)."""
+    return entropy_encoder_frame(u_blocks, 8) + "|" + entropy_encoder_frame(v_blocks, 8)
+
+
+def parse_chroma_residual_line(line: str):
+    """-> (qtc_u, qtc_v), int16 [nb, 64] each."""
+    parts = line.strip().split("|")
+    if len(parts) != 2:
+        raise ValueError("a chroma residual line holds U's blocks, '|', V's blocks")
+    out = []
+    for part in parts:
+        blocks = entropy_decoder_frame(part, 8)
+        if any(s != 0 for s, _ in blocks):
+            raise ValueError("chroma blocks are never split")
+        out.append(np.stack([np.asarray(b) for _, b in blocks]).reshape(len(blocks), 64).astype(np.int16))
+    if out[0].shape != out[1].shape:
+        raise ValueError(f"chroma residual line: {out[0].shape[0]} U blocks against {out[1].shape[0]} V blocks")
+    return out[0], out[1]
+
+
 # ---- per-block QP map line (build extension: ROI / two-pass RC) --------------------------------
 def qp_map_line(qp_map, qp_rows, base_qp, num_blocks_per_row) -> str:
     """Per-block QPs as comma-separated deltas against the row's QP (the per-row QP the

@@ -11,6 +11,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "so_chroma.h"
 #include "so_common.h"
 #include "so_run.h"
 
@@ -1206,6 +1207,99 @@ int so_ssim_u8(const uint8_t* const* a, const uint8_t* const* b, int nframes, in
         SO_NEED(a[i], fn); SO_NEED(b[i], fn);
     }
     return ssim_launch(a, b, nframes, H, W, pitch_a, pitch_b, win, out, workspace, (hipStream_t)stream);
+}
+
+// ---- chroma 4:2:0 (so_chroma.hip) ----------------------------------------------------------------
+static int chroma_frame(const char* fn, bool encode, const uint8_t* cur_u, const uint8_t* cur_v,
+                        const uint8_t* const* refs_u, const uint8_t* const* refs_v, int nref, int H, int W, int bs,
+                        int frame_type, const uint8_t* split, const int16_t* mv, int qp, const int32_t* qp_row,
+                        const int32_t* qp_map, int qp_offset, int16_t* qtc_u, int16_t* qtc_v, int32_t* out_tokens,
+                        uint8_t* out_recon_u, uint8_t* out_recon_v, int32_t* out_sse, void* stream) {
+    if (bs != 16) {
+        set_error("%s: block_size %d not built (chroma follows 16x16 luma blocks)", fn, bs);
+        return SO_E_UNSUPPORTED;
+    }
+    if (H <= 0 || W <= 0 || H % 16 || W % 16) {
+        set_error("%s: luma frame %dx%d must be a positive multiple of 16 (pad with pad_hw)", fn, W, H);
+        return SO_E_INVALID;
+    }
+    if ((long long)H * W > (1ll << 31)) {
+        set_error("%s: frame too large", fn);
+        return SO_E_INVALID;
+    }
+    if (frame_type != 0 && frame_type != 1) {
+        set_error("%s: frame_type %d (0 = intra, 1 = inter)", fn, frame_type);
+        return SO_E_INVALID;
+    }
+    SO_TRY(check_qp(fn, qp));
+    if (qp_offset < -20 || qp_offset > 20) {
+        set_error("%s: qp_offset %d outside [-20, 20]", fn, qp_offset);
+        return SO_E_INVALID;
+    }
+    ChromaArgs a{};
+    if (frame_type == 1) {
+        if (nref < 1 || nref > kMaxRef) {
+            set_error("%s: nref %d outside [1, %d]", fn, nref, kMaxRef);
+            return SO_E_INVALID;
+        }
+        SO_TRY(make_refs(fn, refs_u, nref, &a.pl[0].refs));
+        SO_TRY(make_refs(fn, refs_v, nref, &a.pl[1].refs));
+        SO_NEED(split, fn); SO_NEED(mv, fn);
+    }
+    if (encode) {
+        SO_NEED(cur_u, fn); SO_NEED(cur_v, fn); SO_NEED(out_tokens, fn); SO_NEED(out_sse, fn);
+    }
+    SO_NEED(qtc_u, fn); SO_NEED(qtc_v, fn); SO_NEED(out_recon_u, fn); SO_NEED(out_recon_v, fn);
+    if (out_recon_u == out_recon_v) {
+        set_error("%s: out_recon_u aliases out_recon_v", fn);
+        return SO_E_INVALID;
+    }
+    // rows move as 8-byte vectors and the prediction reads aligned dwords of the planes
+    const uintptr_t planes_or = (uintptr_t)cur_u | (uintptr_t)cur_v | (uintptr_t)out_recon_u | (uintptr_t)out_recon_v;
+    uintptr_t refs_or = 0;
+    if (frame_type == 1)
+        for (int i = 0; i < nref; ++i) {
+            refs_or |= (uintptr_t)refs_u[i] | (uintptr_t)refs_v[i];
+            if (refs_u[i] == out_recon_u || refs_u[i] == out_recon_v || refs_v[i] == out_recon_u ||
+                refs_v[i] == out_recon_v) {
+                set_error("%s: a reconstruction aliases refs[%d]", fn, i);
+                return SO_E_INVALID;
+            }
+        }
+    if (((planes_or | refs_or) & 7) || (((uintptr_t)qtc_u | (uintptr_t)qtc_v) & 15)) {
+        set_error("%s: planes must be 8-byte aligned and qtc 16-byte aligned", fn);
+        return SO_E_INVALID;
+    }
+    a.pl[0].cur = cur_u; a.pl[1].cur = cur_v;
+    a.pl[0].qtc = qtc_u; a.pl[1].qtc = qtc_v;
+    a.pl[0].recon = out_recon_u; a.pl[1].recon = out_recon_v;
+    a.nref = frame_type == 1 ? nref : 1;
+    a.Hc = H / 2; a.Wc = W / 2; a.nbx = W / 16; a.nb = (W / 16) * (H / 16);
+    a.frame_type = frame_type;
+    a.split = split; a.mv = mv;
+    a.qp = qp; a.qp_row = qp_row; a.qp_map = qp_map; a.qp_offset = qp_offset;
+    a.tokens = out_tokens; a.sse = out_sse;
+    return chroma_launch(a, encode, (hipStream_t)stream);
+}
+
+int so_chroma_encode_frame(const uint8_t* cur_u, const uint8_t* cur_v, const uint8_t* const* refs_u,
+                           const uint8_t* const* refs_v, int nref, int H, int W, int bs, int frame_type,
+                           const uint8_t* split, const int16_t* mv, int qp, const int32_t* qp_row,
+                           const int32_t* qp_map, int qp_offset, int16_t* out_qtc_u, int16_t* out_qtc_v,
+                           int32_t* out_tokens, uint8_t* out_recon_u, uint8_t* out_recon_v, int32_t* out_sse,
+                           void* stream) {
+    return chroma_frame("so_chroma_encode_frame", true, cur_u, cur_v, refs_u, refs_v, nref, H, W, bs, frame_type,
+                        split, mv, qp, qp_row, qp_map, qp_offset, out_qtc_u, out_qtc_v, out_tokens, out_recon_u,
+                        out_recon_v, out_sse, stream);
+}
+
+int so_chroma_recon_frame(const uint8_t* const* refs_u, const uint8_t* const* refs_v, int nref, int H, int W, int bs,
+                          int frame_type, const uint8_t* split, const int16_t* mv, int qp, const int32_t* qp_row,
+                          const int32_t* qp_map, int qp_offset, const int16_t* qtc_u, const int16_t* qtc_v,
+                          uint8_t* out_recon_u, uint8_t* out_recon_v, void* stream) {
+    return chroma_frame("so_chroma_recon_frame", false, nullptr, nullptr, refs_u, refs_v, nref, H, W, bs, frame_type,
+                        split, mv, qp, qp_row, qp_map, qp_offset, const_cast<int16_t*>(qtc_u),
+                        const_cast<int16_t*>(qtc_v), nullptr, out_recon_u, out_recon_v, nullptr, stream);
 }
 
 // ---- packed symbol stream (so_pack.hip) -----------------------------------------------------

@@ -13,7 +13,7 @@ import torch
 
 from . import bitstream as _bs
 from .bitstream import entropy_encoder_block  # noqa: F401  (API parity helpers live there)
-from .engine import Engine, alloc_planes
+from .engine import Engine, FrameSymbols, alloc_planes
 
 
 def _canon_frame(frame_type, mvs, residuals, bs):
@@ -61,6 +61,8 @@ class decoder:
         self.ParallelMode = ParallelMode
         self.device = torch.device(device) if device is not None else torch.device("cuda")
         self._engine = None
+        self.decoded_chroma = None          # [(U, V)] host planes of decode_chroma
+        self.decoded_chroma_device = None   # [(U, V)] device planes of decode_symbols
 
     def _eng(self, engine=None) -> Engine:
         if engine is not None:
@@ -75,9 +77,40 @@ class decoder:
     def _rc(self):
         return self.RCFlag is not None and self.RCFlag > 0
 
-    def decode_symbols(self, symbols, engine=None):
-        """GOP decode straight from device symbols (the encoder's closed loop)."""
+    def _chroma_loop(self, eng, syms, qtcs, qp_offset):
+        """The chroma GOP loop: per frame (U, V) device planes from the luma symbols `syms` and
+        the coefficients qtcs[i] = (qtc_u, qtc_v).  The reference list follows the luma one's
+        handling below (one all-128 plane at first, cleared by an I-frame)."""
+        c128 = alloc_planes(1, eng.h // 2, eng.w // 2, eng.device, fill=128)[0]
+        refs_u, refs_v = [c128], [c128]
+        out = []
+        n = len(syms)
+        for i, (s, (qu, qv)) in enumerate(zip(syms, qtcs)):
+            if s.frame_type == 0:
+                refs_u, refs_v = [], []
+            c = eng.recon_chroma(s, qu, qv, refs_u, refs_v, qp_offset)
+            out.append((c.recon_u, c.recon_v))
+            if i < n - 1:
+                if len(refs_u) >= self.nRefFrames:
+                    refs_u.pop(0)
+                    refs_v.pop(0)
+                refs_u.append(c.recon_u)
+                refs_v.append(c.recon_v)
+        return out
+
+    def decode_symbols(self, symbols, engine=None, chroma_symbols=None):
+        """GOP decode straight from device symbols (the encoder's closed loop).  With
+        chroma_symbols (the encoder's ChromaSymbols per frame) U and V are rebuilt too, into
+        self.decoded_chroma_device; the return value stays the luma planes."""
         eng = self._eng(engine)
+        if chroma_symbols is not None:
+            lum = [FrameSymbols(s.frame_type, s.split, s.mv, None, None, None, None, qp_rd=self.Qp,
+                                qp_row=s.qp_row if self._rc() else None,
+                                extra={"qp_map": s.extra["qp_map"]} if "qp_map" in s.extra else {})
+                   for s in symbols]
+            self.decoded_chroma_device = self._chroma_loop(
+                eng, lum, [(c.qtc_u, c.qtc_v) for c in chroma_symbols],
+                chroma_symbols[0].qp_offset if chroma_symbols else 0)
         ref_frames = [alloc_planes(1, eng.h, eng.w, eng.device, fill=128)[0]]
         out = []
         n = len(symbols)
@@ -131,6 +164,59 @@ class decoder:
             self.decoded_vid = host
         return host
 
+    def decode_chroma(self, frame_type_seq, mv_file, chroma_residuals, Qp_per_row_per_frame, qp_maps=None,
+                      chroma_qp_offset=0):
+        """U and V of every frame from the package's per-frame lists: mv_file as decode() takes
+        it (the luma motion), chroma_residuals[i] = (qtc_u, qtc_v) as int16 [nb, 64] arrays or the
+        package's "chroma approx residual" entry.  Returns per-frame (U, V) cropped to the picture."""
+        if self.FMEEnable:
+            raise NotImplementedError("chroma with FMEEnable is not built")
+        if self.block_size != 16:
+            raise NotImplementedError("chroma needs block_size 16")
+        eng = self._eng()
+        syms, qtcs = [], []
+        for i, ft in enumerate(frame_type_seq):
+            nb = len(mv_file[i])
+            split_d = mv_d = None
+            if ft == 1:
+                split = np.zeros(nb, np.uint8)
+                mv = np.zeros((nb, 4, 3), np.int16)
+                for b, m in enumerate(mv_file[i]):
+                    if m[0] == 0:
+                        mv[b, 0] = m[1]
+                    else:
+                        split[b] = 1
+                        mv[b] = m[1]
+                split_d = torch.from_numpy(split).to(eng.device)
+                mv_d = torch.from_numpy(mv).to(eng.device)
+            extra = {}
+            if qp_maps is not None and qp_maps[i] is not None:
+                extra["qp_map"] = torch.as_tensor(np.asarray(qp_maps[i], np.int32)).to(eng.device)
+            syms.append(FrameSymbols(ft, split_d, mv_d, None, None, None, None, qp_rd=self.Qp,
+                                     qp_row=list(Qp_per_row_per_frame[i]) if self._rc() else None, extra=extra))
+            pair = []
+            for q in chroma_residuals[i]:
+                if isinstance(q, list):   # the package's [(0, QTC 8 x 8)] per block
+                    q = np.stack([np.asarray(b) for _, b in q])
+                pair.append(torch.from_numpy(np.ascontiguousarray(np.asarray(q).reshape(nb, 64).astype(np.int16)))
+                            .to(eng.device))
+            qtcs.append(tuple(pair))
+        dev = self._chroma_loop(eng, syms, qtcs, int(chroma_qp_offset))
+        h2, w2 = self.h_pixels // 2, self.w_pixels // 2
+        self.decoded_chroma = [(u.cpu().numpy()[:h2, :w2], v.cpu().numpy()[:h2, :w2]) for u, v in dev]
+        return self.decoded_chroma
+
+    def save_yuv420(self, filename):
+        """The decoded frames as a planar 4:2:0 file (Y | U | V per frame, picture size): needs
+        decode() / decode_bitstream() with chroma."""
+        if not self.decoded_vid_f or self.decoded_chroma is None:
+            raise ValueError("save_yuv420 needs decoded luma and chroma frames")
+        with open(filename, "wb") as f:
+            for y, (u, v) in zip(self.decoded_vid, self.decoded_chroma):
+                f.write(np.ascontiguousarray(y).tobytes())
+                f.write(np.ascontiguousarray(u).tobytes())
+                f.write(np.ascontiguousarray(v).tobytes())
+
     # ---- text bitstream (decoder.py:547-710) ----------------------------------------------
     def entropy_decoder_block(self, encoded_block, block_size):
         return _bs.entropy_decoder_block(encoded_block, block_size)
@@ -156,10 +242,12 @@ class decoder:
         return frame_type_seq, mv_for_vid, qp_for_vid, res_for_vid
 
     def decode_bitstream(self, mv_file, residual_file, intra_mode=None, intra_dur=None, block_size=None, frames=None,
-                         width=None, height=None, save_decoded_frames=True, qp_map_file=None):
+                         width=None, height=None, save_decoded_frames=True, qp_map_file=None,
+                         chroma_residual_file=None, chroma_qp_offset=0):
         """decoder.py:686-709: parse the transmitted text bitstream (transmit_bitstream)
         on the host, reconstruct every frame on the GPU.  qp_map_file: the per-block QP
-        lines of ROI / two-pass RC (build extension)."""
+        lines of ROI / two-pass RC (build extension).  chroma_residual_file: the chroma lines
+        of transmit_bitstream; U and V are then rebuilt too (self.decoded_chroma, save_yuv420)."""
         bs = block_size or self.block_size
         ft, mvs, qps, res = self.decode_differential_entropy(mv_file, residual_file, bs)
         self.mv_per_frame = mvs
@@ -169,8 +257,14 @@ class decoder:
             with open(qp_map_file) as f:
                 maps = [(_bs.parse_qp_map_line(line, qps[i] if self._rc() else None, self.Qp, self.num_blocks_per_row)
                          if line.strip() else None) for i, line in enumerate(f)]
-        return self.decode(ft, res, qps, mvs, intra_mode, intra_dur, bs, frames, width, height, save_decoded_frames,
+        host = self.decode(ft, res, qps, mvs, intra_mode, intra_dur, bs, frames, width, height, save_decoded_frames,
                            qp_maps=maps)
+        if chroma_residual_file is not None:
+            with open(chroma_residual_file) as f:
+                cres = [_bs.parse_chroma_residual_line(line) for line in f if line.strip()]
+            n = len(host)
+            self.decode_chroma(ft[:n], mvs[:n], cres[:n], qps[:n], qp_maps=maps, chroma_qp_offset=chroma_qp_offset)
+        return host
 
     def decode_packed_file(self, path: str, save_decoded_frames=True):
         """Encoder.transmit_packed's file: the packed streams go to the GPU, so_unpack_frames

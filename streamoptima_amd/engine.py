@@ -78,6 +78,19 @@ class FrameSymbols:
     extra: dict = field(default_factory=dict)
 
 
+@dataclass
+class ChromaSymbols:
+    """Per-frame output of the chroma path (include/streamoptima.h so_chroma_encode_frame)."""
+    frame_type: int                    # the luma frame's
+    qtc_u: torch.Tensor                # int16 [nb, 64]
+    qtc_v: torch.Tensor
+    recon_u: torch.Tensor              # uint8 [h/2, w/2]
+    recon_v: torch.Tensor
+    tokens: torch.Tensor | None = None   # int32 [2, nb] (U, V); None from recon_chroma
+    sse: torch.Tensor | None = None      # int32 [2, nb]
+    qp_offset: int = 0
+
+
 class Engine:
     """Kernels for one frame geometry on one device."""
 
@@ -494,6 +507,85 @@ class Engine:
                                         split.data_ptr(), mv.data_ptr(), qtc.data_ptr(), out.data_ptr(),
                                         self.scratch.data_ptr(), _lib.stream_handle(self.device))
         _lib.check(rc, "so_intra_recon_ex")
+        return out
+
+    # ---- chroma 4:2:0 (so_chroma.hip) -----------------------------------------------------
+    def new_chroma_symbols(self, frame_type: int = 0, encode: bool = True) -> ChromaSymbols:
+        d, nb = self.device, self.nb
+        rec = alloc_planes(2, self.h // 2, self.w // 2, d)
+        return ChromaSymbols(frame_type=frame_type,
+                             qtc_u=torch.empty((nb, 64), dtype=torch.int16, device=d),
+                             qtc_v=torch.empty((nb, 64), dtype=torch.int16, device=d),
+                             recon_u=rec[0], recon_v=rec[1],
+                             tokens=torch.empty((2, nb), dtype=torch.int32, device=d) if encode else None,
+                             sse=torch.empty((2, nb), dtype=torch.int32, device=d) if encode else None)
+
+    def _check_chroma_plane(self, t: torch.Tensor, name: str):
+        hc, wc = self.h // 2, self.w // 2
+        if t.dtype != torch.uint8 or t.device != self.device or tuple(t.shape) != (hc, wc) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous uint8 {hc}x{wc} tensor on {self.device}")
+
+    def _chroma_args(self, sym: FrameSymbols, refs_u: list, refs_v: list):
+        """The luma frame's part of a chroma call: references, motion and the QP source."""
+        if self.fme:
+            raise NotImplementedError("chroma with FMEEnable: the luma MVs are in half-pel units")
+        inter = int(sym.frame_type) == 1
+        if inter:
+            if len(refs_u) != len(refs_v):
+                raise ValueError(f"chroma: {len(refs_u)} U references against {len(refs_v)} V references")
+            for k, (ru, rv) in enumerate(zip(refs_u, refs_v)):
+                self._check_chroma_plane(ru, f"refs_u[{k}]")
+                self._check_chroma_plane(rv, f"refs_v[{k}]")
+            if sym.mv.dtype != torch.int16 or tuple(sym.mv.shape) != (self.nb, 4, 3) or sym.split.numel() != self.nb:
+                raise ValueError(f"chroma: the luma symbols must be split [{self.nb}] and int16 mv [{self.nb}, 4, 3]")
+        qm = sym.extra.get("qp_map")
+        if qm is not None and (qm.dtype != torch.int32 or qm.numel() != self.nb or not qm.is_contiguous()):
+            raise ValueError(f"chroma: the QP map must be contiguous int32 [{self.nb}]")
+        qr = self.qp_row_tensor(sym.qp_row) if sym.qp_row else None
+        return (_lib.ref_array(refs_u) if inter else None, _lib.ref_array(refs_v) if inter else None,
+                len(refs_u) if inter else 0, self.h, self.w, self.bs, int(sym.frame_type),
+                sym.split.data_ptr() if inter else None, sym.mv.data_ptr() if inter else None, int(sym.qp_rd),
+                _lib.ptr(qr), _lib.ptr(qm))
+
+    def encode_chroma(self, sym: FrameSymbols, cur_u: torch.Tensor, cur_v: torch.Tensor, refs_u: list, refs_v: list,
+                      qp_offset: int = 0, out: ChromaSymbols | None = None) -> ChromaSymbols:
+        """so_chroma_encode_frame: U and V of the frame whose luma symbols are `sym` (its frame
+        type, split flags and motion vectors, and its QP source: the per-block map in
+        sym.extra["qp_map"], else sym.qp_row, else sym.qp_rd), predicted from refs_u / refs_v --
+        the chroma reconstructions in the luma reference list's order (ignored by an I-frame).
+        One launch, stream-ordered after the luma work that wrote `sym`; asynchronous."""
+        self._check_chroma_plane(cur_u, "cur_u")
+        self._check_chroma_plane(cur_v, "cur_v")
+        args = self._chroma_args(sym, refs_u, refs_v)
+        out = out if out is not None and out.tokens is not None else self.new_chroma_symbols()
+        rc = self.lib.so_chroma_encode_frame(cur_u.data_ptr(), cur_v.data_ptr(), *args, int(qp_offset),
+                                             out.qtc_u.data_ptr(), out.qtc_v.data_ptr(), out.tokens.data_ptr(),
+                                             out.recon_u.data_ptr(), out.recon_v.data_ptr(), out.sse.data_ptr(),
+                                             _lib.stream_handle(self.device))
+        _lib.check(rc, "so_chroma_encode_frame")
+        out.frame_type, out.qp_offset = int(sym.frame_type), int(qp_offset)
+        return out
+
+    def recon_chroma(self, sym: FrameSymbols, qtc_u: torch.Tensor, qtc_v: torch.Tensor, refs_u: list, refs_v: list,
+                     qp_offset: int = 0, out: ChromaSymbols | None = None) -> ChromaSymbols:
+        """so_chroma_recon_frame: the decoder's U and V from the quantised coefficients
+        (int16 [nb, 64] each) and the luma frame's symbols `sym` (only frame_type, split, mv and
+        the QP source are read).  Returns a ChromaSymbols without tokens / sse; asynchronous."""
+        for t, name in ((qtc_u, "qtc_u"), (qtc_v, "qtc_v")):
+            if (t.dtype != torch.int16 or t.numel() != self.nb * 64 or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int16 [{self.nb}, 64] tensor on {self.device}")
+        args = self._chroma_args(sym, refs_u, refs_v)
+        if out is None:
+            rec = alloc_planes(2, self.h // 2, self.w // 2, self.device)
+            out = ChromaSymbols(int(sym.frame_type), qtc_u, qtc_v, rec[0], rec[1])
+        else:
+            out.qtc_u, out.qtc_v, out.tokens, out.sse = qtc_u, qtc_v, None, None
+        rc = self.lib.so_chroma_recon_frame(*args, int(qp_offset), qtc_u.data_ptr(), qtc_v.data_ptr(),
+                                            out.recon_u.data_ptr(), out.recon_v.data_ptr(),
+                                            _lib.stream_handle(self.device))
+        _lib.check(rc, "so_chroma_recon_frame")
+        out.frame_type, out.qp_offset = int(sym.frame_type), int(qp_offset)
         return out
 
     # ---- packed symbol stream (so_pack_frames) --------------------------------------------

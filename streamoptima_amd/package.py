@@ -65,6 +65,8 @@ class LazyPackage(dict):
         self._codec = codec
         self._symbols = symbols
         self._host = None
+        self._lazy = self._LAZY
+        self._chroma = None
         self["block size"] = codec.block_size
         self["num frames"] = codec.frames
         self["height in pixels"] = codec.h_pixels
@@ -81,8 +83,23 @@ class LazyPackage(dict):
             self._host = [symbols_to_host(s) for s in self._symbols]
         return self._host
 
+    def add_chroma(self, chroma_symbols, psnr_u, psnr_v, tokens, qp_offset) -> None:
+        """The chroma entries (chroma=True, build extension): per-frame PSNR of U and V, token
+        counts [U, V], the QP offset, and -- built on first access -- "chroma approx residual":
+        per frame (U blocks, V blocks), each a list of (0, QTC int64 8 x 8) in the layout
+        entropy_encoder_frame takes at block size 8."""
+        self._chroma = chroma_symbols
+        self._lazy = self._LAZY + ("chroma approx residual",)
+        self["PSNR per frame U"] = psnr_u
+        self["PSNR per frame V"] = psnr_v
+        self["chroma tokens per frame"] = tokens
+        self["chroma qp offset"] = qp_offset
+
     def _build(self, key):
         bs = self._codec.block_size
+        if key == "chroma approx residual":
+            return [tuple([(0, b) for b in q.cpu().numpy().astype(np.int64).reshape(-1, 8, 8)]
+                          for q in (c.qtc_u, c.qtc_v)) for c in self._chroma]
         if key == "MVS per Frame":
             return [frame_mvs(h, bs) for h in self._hosts()]
         if key == "approx residual":
@@ -92,17 +109,17 @@ class LazyPackage(dict):
         raise KeyError(key)
 
     def __missing__(self, key):
-        if key in self._LAZY:
+        if key in self._lazy:
             v = self._build(key)
             self[key] = v
             return v
         raise KeyError(key)
 
     def __contains__(self, key):
-        return key in self._LAZY or super().__contains__(key)
+        return key in self._lazy or super().__contains__(key)
 
     def keys(self):
-        return list(super().keys()) + [k for k in self._LAZY if not super().__contains__(k)]
+        return list(super().keys()) + [k for k in self._lazy if not super().__contains__(k)]
 
     def any(self):  # the reference calls encoded_package.any() (Encoder.py:1004)
         return True

@@ -124,6 +124,19 @@ class Video_Manager:
             return None
         return self.vid_frames_yuv444[:, 0, :, :]
 
+    def extract_yuv420_planes(self):
+        """(Y [frames, H, W], U, V [frames, H/2, W/2]) of the 4:2:0 input: the planes a
+        chroma=True encoder takes (Y_Video_codec uv_frame_arr = np.stack([U, V], axis=1))."""
+        if self.v_yuv420 is False:
+            print("[ERROR] No YUV 4:2:0 file available!")
+            return None
+        ny, nu = self.num_y_p_yuv420, self.num_u_p_yuv420
+        h2, w2 = int(self.h_pixels / 2), int(self.w_pixels / 2)
+        f = self.frames
+        src = self.vid_frames_yuv420[:f]
+        return (src[:, :ny].reshape(f, self.h_pixels, self.w_pixels), src[:, ny:ny + nu].reshape(f, h2, w2),
+                src[:, ny + nu:ny + 2 * nu].reshape(f, h2, w2))
+
     def save_y_only(self, filename, y_data_list):
         with open(filename, "wb") as f:
             for data in y_data_list:

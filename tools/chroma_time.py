@@ -1,0 +1,142 @@
+"""Time the chroma path on one MI355X.  Three figures from one run:
+
+  * the chroma encode launch (so_chroma_encode_frame: U and V of one frame) of a 2160 x 3840
+    P-frame on the luma symbols of a real encode -- the median of individually evented calls,
+    warmed -- with the bytes it moves, computed from the shapes, over that time;
+  * the GOP's chroma chain alone (30 dependent launches) replayed from a captured graph, per
+    frame: the device time without the host's per-launch enqueue cost;
+  * the 4K 30-frame I+P GOP (the benchmark's configs[2], workloads.WORKLOADS["4k"]) through
+    Y_Video_codec.encode_device with chroma off and on, evented per GOP, the two alternating.
+
+Prints one JSON line; DESIGN.md "Chroma 4:2:0" quotes it.
+
+    python tools/chroma_time.py [--reps 40] [--gop-reps 12] [--warmup 5]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from streamoptima_amd.Encoder import Y_Video_codec  # noqa: E402
+from streamoptima_amd.engine import alloc_planes  # noqa: E402
+from streamoptima_amd.synth import synth_sequence_torch  # noqa: E402
+from streamoptima_amd.workloads import WORKLOADS  # noqa: E402
+
+HBM_PEAK = 8.0e12   # bytes / s, MI355X
+
+
+def evented(fn, warmup, reps):
+    """milliseconds of each of `reps` calls of fn, every one between its own pair of events"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return times
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=40)
+    ap.add_argument("--gop-reps", type=int, default=12)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("chroma_time.py needs the GPU (a CPU run measures nothing)")
+    dev = torch.device("cuda:0")
+    cfg = WORKLOADS["4k"]
+    h, w, f = cfg["h"], cfg["w"], cfg["frames"]
+
+    def codec(chroma):
+        return Y_Video_codec(h, w, f, 16, 16, cfg["qp"], cfg["intra_dur"], 0, 0.015, False, device=dev, chroma=chroma)
+    off, on = codec(False), codec(True)
+    eng = on.engine()
+    hp, wp = eng.h, eng.w
+    frames = alloc_planes(f, hp, wp, dev, fill=128)
+    frames[:, :h, :w].copy_(synth_sequence_torch(f, h, w, seed=cfg["seed"], device=dev))
+    uv = alloc_planes(2 * f, hp // 2, wp // 2, dev, fill=128).view(f, 2, hp // 2, wp // 2)
+    for p in range(2):
+        uv[:, p, : h // 2, : w // 2].copy_(synth_sequence_torch(f, h // 2, w // 2, seed=cfg["seed"] + 1 + p, device=dev))
+
+    # ---- the GOP with chroma off and on, alternating --------------------------------------
+    def gop(c, **kw):
+        return c.encode_device(frames, cfg["intra_dur"], check=False, **kw)
+    for _ in range(a.warmup):
+        gop(off)
+        res = gop(on, uv_dev=uv)
+    torch.cuda.synchronize()
+    t_off, t_on = [], []
+    for _ in range(a.gop_reps):
+        for times, c, kw in ((t_off, off, {}), (t_on, on, {"uv_dev": uv})):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            gop(c, **kw)
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1))
+    off.engine().check_run()
+    eng.check_run()
+
+    # ---- one frame's chroma launch on that GOP's luma symbols --------------------------------
+    syms, chroma = res["symbols"], res["chroma_symbols"]
+    k = f // 2                       # a P-frame in the middle of the GOP
+    assert syms[k].frame_type == 1
+    out = eng.new_chroma_symbols()
+    refs_u, refs_v = [chroma[k - 1].recon_u], [chroma[k - 1].recon_v]
+
+    def launch():
+        eng.encode_chroma(syms[k], uv[k, 0], uv[k, 1], refs_u, refs_v, out=out)
+    t_k = evented(launch, a.warmup, a.reps)
+    assert torch.equal(out.recon_u, chroma[k].recon_u) and torch.equal(out.qtc_v, chroma[k].qtc_v)
+
+    # ---- the GOP's chroma chain alone, replayed from a captured graph: device time per frame
+    # without the host's enqueue cost (one evented launch above is bounded by it) -------------
+    outs = [eng.new_chroma_symbols() for _ in range(f)]
+    c128 = alloc_planes(1, hp // 2, wp // 2, dev, fill=128)[0]
+
+    def chain():
+        ru, rv = [c128], [c128]
+        for i, s in enumerate(syms):
+            if s.frame_type == 0:
+                ru, rv = [], []
+            c = eng.encode_chroma(s, uv[i, 0], uv[i, 1], ru, rv, out=outs[i])
+            ru, rv = [c.recon_u], [c.recon_v]
+    chain()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        chain()
+    t_chain = evented(graph.replay, a.warmup, a.reps)
+    assert all(torch.equal(o.recon_v, c.recon_v) and torch.equal(o.qtc_u, c.qtc_u) for o, c in zip(outs, chroma))
+    med_chain = statistics.median(t_chain)
+    nb, npx = eng.nb, (hp // 2) * (wp // 2)
+    # per plane: cur and reference read, reconstruction written (1 B / sample each), qtc written
+    # (2 B / sample); per block: split + mv read once per plane, tokens + sse written
+    bytes_frame = 2 * (npx * (1 + 1 + 1 + 2) + nb * (1 + 24 + 4 + 4))
+    med = statistics.median(t_k)
+    print(json.dumps({
+        "tool": "chroma_time", "height": h, "width": w, "frames": f, "reps": a.reps, "gop_reps": a.gop_reps,
+        "chroma_us_per_frame": round(1e3 * med, 2), "chroma_us_per_frame_min": round(1e3 * min(t_k), 2),
+        "chroma_bytes_per_frame": bytes_frame, "chroma_bytes_per_s": round(bytes_frame / (1e-3 * med), 0),
+        "share_of_hbm_peak": round(bytes_frame / (1e-3 * med) / HBM_PEAK, 4),
+        "chain_us_per_frame": round(1e3 * med_chain / f, 2), "chain_us_per_frame_min": round(1e3 * min(t_chain) / f, 2),
+        "chain_bytes_per_s": round(bytes_frame * f / (1e-3 * med_chain), 0),
+        "chain_share_of_hbm_peak": round(bytes_frame * f / (1e-3 * med_chain) / HBM_PEAK, 4),
+        "gop_ms_chroma_off": round(statistics.median(t_off), 3), "gop_ms_chroma_on": round(statistics.median(t_on), 3),
+        "gop_ms_chroma_off_min": round(min(t_off), 3), "gop_ms_chroma_on_min": round(min(t_on), 3),
+    }))
+
+
+if __name__ == "__main__":
+    main()
