@@ -667,8 +667,24 @@ int so_pack_frames_ex(int nframes, const int32_t* frame_types, const uint8_t* co
 /*
  * The inverse (the decoder side of the packed stream): frame i's bytes packed[i] with the
  * block offsets offs[i][0..nb] so_pack_frames wrote, back to split / mv / qtc in the canonical
- * layout (mv entries past an unsplit block's first are 0).  frame_types: HOST array.
- * Malformed input sets the device int32 *err to 1 + a bad block's index (zero it first).
+ * layout (mv entries past the first of an unsplit block are 0 on output).  frame_types: HOST
+ * array.  Malformed input sets the device int32 *err to 1 + a bad block's index (zero it
+ * first); a bad block's outputs are unspecified.  Block b is decoded from exactly its bytes
+ * [offs[b], offs[b+1]); offs[b+1] < offs[b] is malformed, and within the block:
+ *   * a varint is 1-5 bytes, decoded with no bits dropped and then un-zigzagged; a sixth
+ *     continuation byte, or a varint running off the end of the block's bytes, is malformed;
+ *   * split is 0, or 1 at block size 16; anything else is malformed;
+ *   * every mv value and every coefficient lies in [-32768, 32767], else malformed;
+ *   * a token -L needs 1 <= L <= nn - k, a token Z > 0 needs Z <= nn - k (k: the coefficients
+ *     of the (sub-)block covered so far, nn its size); a token 0 ends the (sub-)block, and a
+ *     list also ends at k == nn;
+ *   * all the block's bytes must be consumed.
+ * Accepted though not canonical (unambiguous, never written by so_pack_frames):
+ *   * an over-long varint of up to 5 bytes whose value fits;
+ *   * a 0 value inside a -L list;
+ *   * a zero run that reaches exactly nn written as Z instead of 0.
+ * Offsets that point outside packed[i]'s buffer are a caller precondition, not checked here
+ * (packedfile.read rejects files whose lengths do not add up).
  */
 int so_unpack_frames(int nframes, const int32_t* frame_types, const uint8_t* const* packed,
                      const uint32_t* const* offs, int nb, int block_size, uint8_t* const* split,

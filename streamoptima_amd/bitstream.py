@@ -229,6 +229,8 @@ def varints(buf) -> np.ndarray:
         raise ValueError("packed stream ends inside a varint")
     starts = np.concatenate(([0], ends[:-1] + 1))
     lens = ends - starts + 1
+    if int(lens.max()) > 5:
+        raise ValueError("a varint of more than 5 bytes in the packed stream")
     z = np.zeros(ends.size, dtype=np.int64)
     for k in range(int(lens.max())):
         m = lens > k
@@ -238,8 +240,27 @@ def varints(buf) -> np.ndarray:
 
 def unpack_frame(buf, nb: int, bs: int, frame_type: int) -> dict:
     """One frame's packed stream -> {"split", "mv", "qtc"} in the canonical symbol layout
-    (mv entries past the first of an unsplit block stay 0)."""
-    v = varints(buf).tolist()
+    (mv entries past the first of an unsplit block are 0).  Raises ValueError on malformed
+    input, by the rules of so_unpack_frames (include/streamoptima.h):
+      * a varint is 1-5 bytes; a sixth continuation byte, or a varint running off the end of
+        the bytes, is malformed;
+      * split is 0, or 1 at block size 16; anything else is malformed;
+      * every mv value and every coefficient lies in [-32768, 32767], else malformed;
+      * a token -L needs 1 <= L <= nn - k, a token Z > 0 needs Z <= nn - k (k: the coefficients
+        of the (sub-)block covered so far, nn its size); a token 0 ends the (sub-)block, and a
+        list also ends at k == nn;
+      * all bytes must be consumed.
+    Accepted though not canonical (unambiguous, never written by so_pack_frames): an over-long
+    varint of up to 5 bytes whose value fits, a 0 value inside a -L list, a zero run that
+    reaches exactly nn written as Z instead of 0.  Block boundaries are not known here, so a
+    varint or a list running from one block into the next is seen only where the stream stops
+    parsing."""
+    va = varints(buf)
+    # whatever its role (split, mv, token, coefficient), no value of a well-formed stream
+    # leaves int16
+    if va.size and (int(va.min()) < -32768 or int(va.max()) > 32767):
+        raise ValueError("a value outside int16 in the packed stream")
+    v = va.tolist()
     inter = frame_type == 1
     split = np.zeros(nb, dtype=np.uint8)
     mv = np.zeros((nb, 4, 3) if inter else (nb, 4), dtype=np.int16)
@@ -250,25 +271,31 @@ def unpack_frame(buf, nb: int, bs: int, frame_type: int) -> dict:
         for b in range(nb):
             sp = v[p]
             p += 1
+            if sp != 0 and not (sp == 1 and bs == 16):
+                raise ValueError(f"block {b}: split {sp}")
             split[b] = sp
-            for j in range(4 if sp else 1):
-                if inter:
-                    mv[b, j] = v[p:p + 3]
-                    p += 3
-                else:
-                    mv[b, j] = v[p]
-                    p += 1
+            nmv = (4 if sp else 1) * (3 if inter else 1)
+            if p + nmv > len(v):
+                raise IndexError
+            mv[b].reshape(-1)[:nmv] = v[p:p + nmv]
+            p += nmv
             for n, off in ([(sb, j * sb * sb) for j in range(4)] if sp else [(bs, 0)]):
                 order, k = scan_order(n), 0
                 while k < n * n:
                     t = v[p]
                     p += 1
                     if t < 0:
+                        if -t > n * n - k:
+                            raise ValueError(f"block {b}: a list of {-t} values at position {k} of {n * n}")
+                        if p - t > len(v):
+                            raise IndexError
                         qtc[b, off + order[k:k - t]] = v[p:p - t]
                         p, k = p - t, k - t
                     elif t == 0:
                         break
                     else:
+                        if t > n * n - k:
+                            raise ValueError(f"block {b}: a run of {t} zeros at position {k} of {n * n}")
                         k += t
     except IndexError:
         raise ValueError(f"packed stream ends inside block {b}") from None

@@ -14,6 +14,22 @@
 // run), and a list ends after n*n coefficients otherwise.  bitstream.unpack_frame restores
 // the lists and MVs on the host.
 //
+// What a decoder (unpack_block_kernel, bitstream.unpack_frame) takes as malformed -- the
+// specification is tests/packref.py unpack_block_strict:
+//   * a varint is 1-5 bytes, decoded with no bits dropped and then un-zigzagged; a sixth
+//     continuation byte, or a varint running off the end of the block's bytes, is malformed;
+//   * split is 0, or 1 at block size 16; anything else is malformed;
+//   * every mv value and every coefficient lies in [-32768, 32767], else malformed;
+//   * a token -L needs 1 <= L <= nn - k, a token Z > 0 needs Z <= nn - k (k: the coefficients
+//     of the (sub-)block covered so far, nn its size); a token 0 ends the (sub-)block, and a
+//     list also ends at k == nn;
+//   * all the block's bytes must be consumed.
+// Accepted though not canonical (unambiguous, never written by so_pack_frames):
+//   * an over-long varint of up to 5 bytes whose value fits;
+//   * a 0 value inside a -L list;
+//   * a zero run that reaches exactly nn written as Z instead of 0.
+// mv entries past the first of an unsplit block are 0 on output.
+//
 // Two passes over the frame (one wave per block): byte counts, an exclusive scan per frame
 // (one workgroup), then the bytes at their offsets.  HBM-bound: the dense QTC read once per
 // pass (2 B/px) against the packed stream written once.  A block whose bytes would pass the
@@ -302,8 +318,9 @@ __global__ void __launch_bounds__(1024) pack_scan_kernel(const PackArgs a, int n
 // ---- unpack (so_unpack_frames): the packed stream back to split / mv / qtc ----------------
 // One thread per block parses its bytes [offs[b], offs[b+1]) sequentially: the header, then
 // each (sub-)block's tokens -- "-L" and L values, "Z" zeros, "0" the trailing zeros -- into
-// the zeroed block in scan order.  Malformed input (a varint or token list running past the
-// block's bytes, bytes left over, a run past n*n) sets *err = 1 + that block's index.
+// the zeroed block in scan order.  Malformed input (the rules at the top of this file; also
+// offs[b + 1] < offs[b]) sets *err = 1 + that block's index.  Offsets that point outside the
+// stream's buffer are the caller's to exclude (packedfile.read does).
 struct UnpackFrame {
     const uint8_t* in;
     const uint32_t* offs;
@@ -324,13 +341,22 @@ __global__ void __launch_bounds__(256) unpack_block_kernel(const UnpackArgs a, i
     const uint8_t* p = f.in + f.offs[b];
     const uint8_t* const end = f.in + f.offs[b + 1];
     bool bad = f.offs[b + 1] < f.offs[b];
+    // A varint of 1-5 bytes.  Whatever its role, no value of a well-formed block leaves int16
+    // (split 0 / 1, |token| <= n*n <= 256, mv values and coefficients int16), i.e. zz < 2^16:
+    // the first three bytes carry 21 bits, any payload bit of the fourth and fifth byte (kept
+    // apart in `hi`, so none is shifted out) or of bits 16-20 makes the block malformed, and
+    // what is returned always fits the int16 it is stored to.
     auto next = [&]() -> int {
-        uint32_t z = 0;
+        uint32_t z = 0, hi = 0;
         for (int sh = 0; sh < 35; sh += 7) {
             if (p >= end) break;
             const uint32_t c = *p++;
-            z |= (c & 0x7Fu) << sh;
-            if (!(c & 0x80u)) return (int)(z >> 1) ^ -(int)(z & 1u);
+            if (sh < 21) z |= (c & 0x7Fu) << sh;
+            else hi |= c & 0x7Fu;
+            if (!(c & 0x80u)) {
+                if (hi | (z >> 16)) break;
+                return (int)(z >> 1) ^ -(int)(z & 1u);
+            }
         }
         bad = true;
         return 0;

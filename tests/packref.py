@@ -1,7 +1,9 @@
 """Test helper: a plain-Python writer of the packed symbol stream (so_pack.hip's format), the
 checker for so_pack_frames.  Per block: split, mv values, then each (sub-)block's RLE token
 list produced by the reference's own loop (entropy_encoder_block, Encoder.py:1086-1131,
-restated with its flag / run variables), every number a zigzag LEB128 varint."""
+restated with its flag / run variables), every number a zigzag LEB128 varint.
+unpack_block_strict is the specification of what a decoder accepts: the checker for
+so_unpack_frames and bitstream.unpack_frame."""
 import numpy as np
 
 
@@ -87,3 +89,118 @@ def random_symbols(rng, nb: int, bs: int, frame_type: int, vbs: bool):
         elif kind == 4:
             qtc[b, 0] = rng.integers(-3, 4)
     return split, mv, qtc
+
+
+class _Malformed(Exception):
+    pass
+
+
+def _reader(data: bytes):
+    """next() over the varints of `data` by the strict rules; next.pos is the read position."""
+    def nxt() -> int:
+        z = 0
+        for i in range(5):
+            if nxt.pos >= len(data):
+                raise _Malformed("the bytes end inside a varint")
+            c = data[nxt.pos]
+            nxt.pos += 1
+            z |= (c & 0x7F) << (7 * i)          # a Python int: no bits dropped
+            if not c & 0x80:
+                return z >> 1 if not z & 1 else -(z >> 1) - 1
+        raise _Malformed("a sixth varint byte")
+    nxt.pos = 0
+    return nxt
+
+
+def _walk_block(data: bytes, bs: int, frame_type: int, visit=None) -> dict:
+    """The strict decoder; visit(role, start, end, value, k, nn) sees every varint read."""
+    from streamoptima_amd.bitstream import scan_order
+    nxt = _reader(data)
+
+    def read(role, k=0, nn=0):
+        start = nxt.pos
+        v = nxt()
+        if visit:
+            visit(role, start, nxt.pos, v, k, nn)
+        return v
+
+    def int16(v):
+        if not -32768 <= v <= 32767:
+            raise _Malformed(f"{v} outside int16")
+        return v
+
+    inter = frame_type == 1
+    sp = read("split")
+    if sp != 0 and not (sp == 1 and bs == 16):
+        raise _Malformed(f"split {sp}")
+    mv = np.zeros((4, 3) if inter else 4, np.int16)
+    for j in range(4 if sp else 1):
+        if inter:
+            mv[j] = [int16(read("mv")) for _ in range(3)]
+        else:
+            mv[j] = int16(read("mv"))
+    qtc = np.zeros(bs * bs, np.int16)
+    n = bs // 2 if sp else bs
+    nn, order = n * n, scan_order(n)
+    for j in range(4 if sp else 1):
+        k = 0
+        while k < nn:
+            t = read("token", k, nn)
+            if t < 0:
+                if -t > nn - k:
+                    raise _Malformed(f"a list of {-t} values at position {k} of {nn}")
+                for i in range(-t):
+                    qtc[j * nn + order[k + i]] = int16(read("coef"))
+                k -= t
+            elif t == 0:
+                break
+            else:
+                if t > nn - k:
+                    raise _Malformed(f"a run of {t} zeros at position {k} of {nn}")
+                k += t
+    if nxt.pos != len(data):
+        raise _Malformed(f"{len(data) - nxt.pos} bytes left over")
+    return {"split": sp, "mv": mv, "qtc": qtc}
+
+
+def unpack_block_strict(data, bs: int, frame_type: int):
+    """The specification of the packed stream's block format: exactly one block decoded from
+    exactly its bytes -> {"split": int, "mv": int16 [4, 3] (inter) or [4] (intra), "qtc": int16
+    [bs * bs]}, or None when the bytes are malformed.  Written for clarity, not speed.
+
+    Malformed:
+      * a varint is 1-5 bytes, decoded with no bits dropped and then un-zigzagged; a sixth
+        continuation byte, or a varint running off the end of the block's bytes, is malformed;
+      * split is 0, or 1 at block size 16; anything else is malformed;
+      * every mv value and every coefficient lies in [-32768, 32767], else malformed;
+      * a token -L needs 1 <= L <= nn - k, a token Z > 0 needs Z <= nn - k (k: the coefficients
+        of the (sub-)block covered so far, nn its size); a token 0 ends the (sub-)block, and a
+        list also ends at k == nn;
+      * all the block's bytes must be consumed.
+    Accepted though not canonical (unambiguous, never written by so_pack_frames):
+      * an over-long varint of up to 5 bytes whose value fits;
+      * a 0 value inside a -L list;
+      * a zero run that reaches exactly nn written as Z instead of 0.
+    mv entries past the first of an unsplit block are 0 on output."""
+    try:
+        return _walk_block(bytes(data), bs, frame_type)
+    except _Malformed:
+        return None
+
+
+def block_layout(data, bs: int, frame_type: int) -> list:
+    """The varints of one well-formed block: [(role, start, end, value, k, nn)], role one of
+    "split" / "mv" / "token" / "coef"; for a token, k coefficients of nn are covered before it."""
+    out = []
+    _walk_block(bytes(data), bs, frame_type, lambda *a: out.append(a))
+    return out
+
+
+def varint_padded(v: int, nbytes: int) -> bytes:
+    """v as an over-long varint of exactly nbytes bytes (zero payload in the padding)."""
+    raw = bytearray(varint(v))
+    assert len(raw) <= nbytes
+    while len(raw) < nbytes:
+        raw[-1] |= 0x80
+        raw.append(0)
+    return bytes(raw)
