@@ -690,6 +690,56 @@ int so_unpack_frames(int nframes, const int32_t* frame_types, const uint8_t* con
                      const uint32_t* const* offs, int nb, int block_size, uint8_t* const* split,
                      int16_t* const* mv, int16_t* const* qtc, int32_t* err, void* stream);
 
+/*
+ * The same stream in the "bits" coding: the same symbols per block, in the same order, as
+ * bit-granular Exp-Golomb codes instead of varints (about half the bytes).  Blocks stay
+ * byte-aligned, so the offsets, the totals, the capacity guard and the parallel decode work as
+ * above.  The format (the model is tests/packbitsref.py):
+ *
+ * Bits are written MSB-first within each byte.  With zz(v) = 2v for v >= 0 and -2v-1 otherwise:
+ *   ue(z):    let m = z + 1 and n = bit_length(m); n - 1 zero bits, then m in n bits.
+ *   ue_k(z):  ue(z >> k) followed by the low k bits of z.
+ *   se(v) = ue(zz(v)),  se_k(v) = ue_k(zz(v)).
+ *   -32768 is the longest value at 33 bits: code lengths cross 32 and, accumulated, 64 bits.
+ * One block, in raster order:
+ *   1. split: 1 bit.
+ *   2. k: 2 bits, the order of this block's coefficient codes.
+ *   3. The mv values, se each; the same values and order as the varint format: inter
+ *      (dx, dy, ref) once, or 4x in Z order when split; intra dx once or 4x.
+ *   4. Each (sub-)block's token list exactly as in the varint format ("-L" then L values, "Z",
+ *      a trailing "0").  Tokens are se, coefficient values se_k.
+ *   5. Zero bits up to the next byte boundary.
+ * Canonical k (what so_pack_frames_bits writes): the k in 0..3 that minimises the block's
+ * total coefficient bits; ties go to the smallest k; a block with no coefficient writes 0.
+ * Malformed to a decoder (so_unpack_frames_bits, bitstream.unpack_frame_bits):
+ *   * a ue prefix of more than 16 zero bits;
+ *   * a decoded z > 65535 (so every mv value and coefficient lies in int16);
+ *   * a code running past the block's last byte;
+ *   * split = 1 at block size 8;
+ *   * the token rules as above (-L needs 1 <= L <= nn - k', Z > 0 needs Z <= nn - k', 0 ends
+ *     the list, a list also ends at nn; k': the coefficients covered so far);
+ *   * after the last list, 8 or more bits left, or any set bit among them;
+ *   * offs[b+1] < offs[b].
+ * Accepted though never written: a non-minimal k; k != 0 with no coefficients; a 0 value
+ * inside a -L list; a zero run reaching exactly nn written as Z.
+ * mv entries past the first of an unsplit block are 0 on output.
+ *
+ * so_pack_bits_bound(nb, bs) = nb * ceil((3 + 12*33 + 33*nn + 19*(nn/2 + 4)) / 8), nn = bs^2;
+ *   0 for nb <= 0 or bs other than 8 or 16.  Loose on purpose, like so_pack_bound; at bs 16
+ *   about 1.4 KB per block, so a block's length fits a container's u16.
+ * so_pack_frames_bits: arguments and behaviour of so_pack_frames_ex (totals may be NULL).
+ * so_unpack_frames_bits: arguments and behaviour of so_unpack_frames.
+ */
+size_t so_pack_bits_bound(int nb, int block_size);
+int so_pack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t* const* split,
+                        const int16_t* const* mv, const int16_t* const* qtc, int nb, int block_size,
+                        uint32_t* const* offs, uint8_t* const* out, unsigned long long cap,
+                        uint32_t* totals, void* stream);
+int so_unpack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t* const* packed,
+                          const uint32_t* const* offs, int nb, int block_size,
+                          uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc,
+                          int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

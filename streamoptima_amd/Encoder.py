@@ -690,10 +690,11 @@ class Y_Video_codec(BlockAPI):
     def get_encoded_package(self):
         return self.encoded_package
 
-    def transmit_packed(self, path: str) -> int:
-        """The encoded GOP as one binary file of packed symbols (packedfile.py: varint split /
-        MVs / RLE token lists packed on the GPU by so_pack_frames, ~2.4x smaller than the
-        int16 QTC and far smaller than the text lines).  decoder.decode_packed_file reads it.
+    def transmit_packed(self, path: str, coding: str = "varint") -> int:
+        """The encoded GOP as one binary file of packed symbols (packedfile.py: split / MVs /
+        RLE token lists packed on the GPU, far smaller than the int16 QTC and the text lines).
+        coding "varint": so_pack_frames, every number a varint; "bits": so_pack_frames_bits,
+        Exp-Golomb codes, about half the bytes.  decoder.decode_packed_file reads either.
         Returns the file size in bytes."""
         if self.chroma:
             raise NotImplementedError("the packed container carries luma only: chroma is not built there "
@@ -702,7 +703,8 @@ class Y_Video_codec(BlockAPI):
             print("[ERROR] No encoded package available, please run encode() first")
             return 0
         from . import packedfile
-        return packedfile.write(path, self.engine(), self._symbols, self.encoded_package["Qp_per_row_per_frame"])
+        return packedfile.write(path, self.engine(), self._symbols, self.encoded_package["Qp_per_row_per_frame"],
+                                coding=coding)
 
     def transmit_bitstream(self, intra_dur=None, block_size=None, mv_file=None, residual_file=None,
                            qp_map_file=None, chroma_residual_file=None):

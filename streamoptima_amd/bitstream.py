@@ -304,6 +304,74 @@ def unpack_frame(buf, nb: int, bs: int, frame_type: int) -> dict:
     return {"split": split, "mv": mv, "qtc": qtc}
 
 
+def unpack_frame_bits(buf, nb: int, bs: int, frame_type: int) -> dict:
+    """One frame's packed stream in the "bits" coding (so_pack_frames_bits; the format is in
+    include/streamoptima.h) -> {"split", "mv", "qtc"} as unpack_frame.  Parses sequentially and
+    skips to the next byte boundary after each block, so it needs no offsets.  Raises
+    ValueError on malformed input, by the rules of so_unpack_frames_bits: a ue prefix of more
+    than 16 zero bits, a decoded z > 65535, a code running past the last byte, split = 1 at
+    block size 8, the token rules of unpack_frame, a set pad bit, bytes after the last block."""
+    data = bytes(np.asarray(buf, dtype=np.uint8).reshape(-1))
+    nbits = 8 * len(data)
+    pos = 0
+
+    def peek(n: int) -> int:
+        """The next n <= 40 bits (zeros past the end)."""
+        by = pos >> 3
+        w = int.from_bytes(data[by:by + 8].ljust(8, b"\0"), "big")
+        return (w >> (64 - (pos & 7) - n)) & ((1 << n) - 1)
+
+    def take(n: int) -> int:
+        nonlocal pos
+        if pos + n > nbits:
+            raise ValueError("packed stream ends inside a code")
+        v = peek(n)
+        pos += n
+        return v
+
+    def ue(k: int = 0) -> int:
+        zeros = 17 - peek(17).bit_length()       # zeros past the end: caught by take
+        if zeros > 16:
+            raise ValueError("a prefix of more than 16 zero bits in the packed stream")
+        z = take(2 * zeros + 1 + k) - (1 << k)
+        if z > 65535:
+            raise ValueError("a value outside int16 in the packed stream")
+        return (z >> 1) ^ -(z & 1)
+
+    inter = frame_type == 1
+    split = np.zeros(nb, dtype=np.uint8)
+    mv = np.zeros((nb, 4, 3) if inter else (nb, 4), dtype=np.int16)
+    qtc = np.zeros((nb, bs * bs), dtype=np.int16)
+    sb = bs // 2
+    for b in range(nb):
+        sp, kk = take(1), take(2)
+        if sp and bs != 16:
+            raise ValueError(f"block {b}: split at block size {bs}")
+        split[b] = sp
+        nmv = (4 if sp else 1) * (3 if inter else 1)
+        mv[b].reshape(-1)[:nmv] = [ue() for _ in range(nmv)]
+        for n, off in ([(sb, j * sb * sb) for j in range(4)] if sp else [(bs, 0)]):
+            order, k = scan_order(n), 0
+            while k < n * n:
+                t = ue()
+                if t < 0:
+                    if -t > n * n - k:
+                        raise ValueError(f"block {b}: a list of {-t} values at position {k} of {n * n}")
+                    qtc[b, off + order[k:k - t]] = [ue(kk) for _ in range(-t)]
+                    k -= t
+                elif t == 0:
+                    break
+                else:
+                    if t > n * n - k:
+                        raise ValueError(f"block {b}: a run of {t} zeros at position {k} of {n * n}")
+                    k += t
+        if take(-pos % 8):
+            raise ValueError(f"block {b}: a set bit in the padding")
+    if pos != nbits:
+        raise ValueError(f"{(nbits - pos) // 8} bytes after the last block")
+    return {"split": split, "mv": mv, "qtc": qtc}
+
+
 # ---- chroma residual line (build extension: chroma 4:2:0) ------------------------------------------
 def chroma_residual_line(u_blocks, v_blocks) -> str:
     """One frame's chroma coefficients: U's entropy_encoder_frame line at block size 8, '|', V's

@@ -73,6 +73,10 @@ struct UnpackFrame {
 int unpack_frames_launch(const UnpackFrame* frames, int nframes, int nb, int bs, int32_t* err, hipStream_t st);
 int pack_frames_launch(const PackFrame* frames, int nframes, int nb, int bs, unsigned long long cap, uint32_t* totals,
                        hipStream_t st);
+size_t pack_bits_block_bound(int bs);   // so_packbits.hip
+int unpack_bits_frames_launch(const UnpackFrame* frames, int nframes, int nb, int bs, int32_t* err, hipStream_t st);
+int pack_bits_frames_launch(const PackFrame* frames, int nframes, int nb, int bs, unsigned long long cap,
+                            uint32_t* totals, hipStream_t st);
 int stripe_halo_push_launch(const uint8_t* plane, int W, int by0, int by1, uint8_t* up, uint8_t* dn,
                             uint32_t* up_flags, uint32_t* dn_flags, int gf, uint32_t epoch, hipStream_t st);
 int frame_push_launch(const uint8_t* plane, int H, int W, uint8_t* dst, uint32_t* flags, uint32_t epoch,
@@ -1314,10 +1318,11 @@ int so_pack_frames(int nframes, const int32_t* frame_types, const uint8_t* const
     return so_pack_frames_ex(nframes, frame_types, split, mv, qtc, nb, bs, offs, out, cap, nullptr, stream);
 }
 
-int so_pack_frames_ex(int nframes, const int32_t* frame_types, const uint8_t* const* split, const int16_t* const* mv,
-                      const int16_t* const* qtc, int nb, int bs, uint32_t* const* offs, uint8_t* const* out,
-                      unsigned long long cap, uint32_t* totals, void* stream) {
-    const char* fn = "so_pack_frames";
+// validation and launch of both codings of the stream (bits: so_packbits.hip)
+static int pack_frames_any(const char* fn, bool bits, int nframes, const int32_t* frame_types,
+                           const uint8_t* const* split, const int16_t* const* mv, const int16_t* const* qtc, int nb,
+                           int bs, uint32_t* const* offs, uint8_t* const* out, unsigned long long cap,
+                           uint32_t* totals, void* stream) {
     if (bs != 16 && bs != 8) {
         set_error("%s: block_size %d not built", fn, bs);
         return SO_E_UNSUPPORTED;
@@ -1337,13 +1342,14 @@ int so_pack_frames_ex(int nframes, const int32_t* frame_types, const uint8_t* co
         }
         fr[i] = PackFrame{split[i], mv[i], qtc[i], offs[i], out[i], frame_types[i]};
     }
-    return pack_frames_launch(fr.data(), nframes, nb, bs, cap, totals, (hipStream_t)stream);
+    return bits ? pack_bits_frames_launch(fr.data(), nframes, nb, bs, cap, totals, (hipStream_t)stream)
+                : pack_frames_launch(fr.data(), nframes, nb, bs, cap, totals, (hipStream_t)stream);
 }
 
-int so_unpack_frames(int nframes, const int32_t* frame_types, const uint8_t* const* packed, const uint32_t* const* offs,
-                     int nb, int bs, uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc, int32_t* err,
-                     void* stream) {
-    const char* fn = "so_unpack_frames";
+static int unpack_frames_any(const char* fn, bool bits, int nframes, const int32_t* frame_types,
+                             const uint8_t* const* packed, const uint32_t* const* offs, int nb, int bs,
+                             uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc, int32_t* err,
+                             void* stream) {
     if (bs != 16 && bs != 8) {
         set_error("%s: block_size %d not built", fn, bs);
         return SO_E_UNSUPPORTED;
@@ -1364,7 +1370,42 @@ int so_unpack_frames(int nframes, const int32_t* frame_types, const uint8_t* con
         }
         fr[i] = UnpackFrame{packed[i], offs[i], split[i], mv[i], qtc[i], frame_types[i]};
     }
-    return unpack_frames_launch(fr.data(), nframes, nb, bs, err, (hipStream_t)stream);
+    return bits ? unpack_bits_frames_launch(fr.data(), nframes, nb, bs, err, (hipStream_t)stream)
+                : unpack_frames_launch(fr.data(), nframes, nb, bs, err, (hipStream_t)stream);
+}
+
+int so_pack_frames_ex(int nframes, const int32_t* frame_types, const uint8_t* const* split, const int16_t* const* mv,
+                      const int16_t* const* qtc, int nb, int bs, uint32_t* const* offs, uint8_t* const* out,
+                      unsigned long long cap, uint32_t* totals, void* stream) {
+    return pack_frames_any("so_pack_frames", false, nframes, frame_types, split, mv, qtc, nb, bs, offs, out, cap, totals,
+                           stream);
+}
+
+int so_unpack_frames(int nframes, const int32_t* frame_types, const uint8_t* const* packed, const uint32_t* const* offs,
+                     int nb, int bs, uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc, int32_t* err,
+                     void* stream) {
+    return unpack_frames_any("so_unpack_frames", false, nframes, frame_types, packed, offs, nb, bs, split, mv, qtc, err,
+                             stream);
+}
+
+// ---- the same stream in the "bits" coding (so_packbits.hip) ---------------------------------
+size_t so_pack_bits_bound(int nb, int bs) {
+    if (nb <= 0 || (bs != 16 && bs != 8)) return 0;
+    return (size_t)nb * pack_bits_block_bound(bs);
+}
+
+int so_pack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t* const* split,
+                        const int16_t* const* mv, const int16_t* const* qtc, int nb, int bs, uint32_t* const* offs,
+                        uint8_t* const* out, unsigned long long cap, uint32_t* totals, void* stream) {
+    return pack_frames_any("so_pack_frames_bits", true, nframes, frame_types, split, mv, qtc, nb, bs, offs, out, cap,
+                           totals, stream);
+}
+
+int so_unpack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t* const* packed,
+                          const uint32_t* const* offs, int nb, int bs, uint8_t* const* split, int16_t* const* mv,
+                          int16_t* const* qtc, int32_t* err, void* stream) {
+    return unpack_frames_any("so_unpack_frames_bits", true, nframes, frame_types, packed, offs, nb, bs, split, mv, qtc,
+                             err, stream);
 }
 
 }  // extern "C"

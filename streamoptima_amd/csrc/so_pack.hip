@@ -315,6 +315,11 @@ __global__ void __launch_bounds__(1024) pack_scan_kernel(const PackArgs a, int n
     }
 }
 
+// the scan for the other coding of the stream (so_packbits.hip), whose byte counts it scans alike
+void pack_scan_launch(const PackArgs& a, int nframes, int nb, uint32_t* totals, hipStream_t st) {
+    hipLaunchKernelGGL(pack_scan_kernel, dim3(nframes), dim3(1024), 0, st, a, nb, totals);
+}
+
 // ---- unpack (so_unpack_frames): the packed stream back to split / mv / qtc ----------------
 // One thread per block parses its bytes [offs[b], offs[b+1]) sequentially: the header, then
 // each (sub-)block's tokens -- "-L" and L values, "Z" zeros, "0" the trailing zeros -- into

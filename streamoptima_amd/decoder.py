@@ -267,15 +267,15 @@ class decoder:
         return host
 
     def decode_packed_file(self, path: str, save_decoded_frames=True):
-        """Encoder.transmit_packed's file: the packed streams go to the GPU, so_unpack_frames
-        restores split / mv / qtc of every block in parallel, and the frames are rebuilt by the
-        same kernels as decode()."""
+        """Encoder.transmit_packed's file: the packed streams go to the GPU, so_unpack_frames (or
+        so_unpack_frames_bits, by the file's version) restores split / mv / qtc of every block
+        in parallel, and the frames are rebuilt by the same kernels as decode()."""
         from . import packedfile
         eng = self._eng()
         meta = packedfile.read(path, eng.device)
         if (meta["h"], meta["w"], meta["bs"], meta["nb"]) != (eng.h, eng.w, eng.bs, eng.nb):
             raise ValueError(f"{path}: {meta['w']}x{meta['h']} bs {meta['bs']} does not match this decoder")
-        syms = eng.unpack_symbols(meta["frame_types"], meta["packed"], meta["offs"])
+        syms = eng.unpack_symbols(meta["frame_types"], meta["packed"], meta["offs"], coding=meta["coding"])
         for s, q in zip(syms, meta["qp_rows"]):
             s.qp_row = q or None
         decoded = self.decode_symbols(syms, eng)

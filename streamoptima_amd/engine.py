@@ -62,6 +62,13 @@ def ssim_planes(lib, device, a_planes, b_planes, h: int, w: int, win: int, out, 
     return out
 
 
+def pack_coding_is_bits(coding: str) -> bool:
+    """The packed stream's codings: False for "varint", True for "bits"; anything else raises."""
+    if coding not in ("varint", "bits"):
+        raise ValueError(f"packed stream coding {coding!r} (\"varint\" or \"bits\")")
+    return coding == "bits"
+
+
 @dataclass
 class FrameSymbols:
     """Per-frame output of the encode path (canonical layout, include/streamoptima.h)."""
@@ -588,25 +595,29 @@ class Engine:
         out.frame_type, out.qp_offset = int(sym.frame_type), int(qp_offset)
         return out
 
-    # ---- packed symbol stream (so_pack_frames) --------------------------------------------
-    def pack_bound(self, nb: int | None = None) -> int:
-        return int(self.lib.so_pack_bound(int(self.nb if nb is None else nb), self.bs))
+    # ---- packed symbol stream (so_pack_frames / so_pack_frames_bits) -----------------------
+    def pack_bound(self, nb: int | None = None, coding: str = "varint") -> int:
+        bound = self.lib.so_pack_bits_bound if pack_coding_is_bits(coding) else self.lib.so_pack_bound
+        return int(bound(int(self.nb if nb is None else nb), self.bs))
 
     def pack_symbols(self, syms: list, offs: torch.Tensor | None = None, out: torch.Tensor | None = None,
-                     totals_ptr: int | None = None):
+                     totals_ptr: int | None = None, coding: str = "varint"):
         """Each frame's symbols as one packed byte stream on the device (include/streamoptima.h
         so_pack_frames); asynchronous.  Returns (offs int32 [n, nb + 1], out uint8 [n, cap]):
         frame i's stream is out[i, :offs[i, nb]], block b starts at offs[i, b]
         (bitstream.unpack_frame decodes it).  The default capacity never overflows.
         totals_ptr: a device address of n uint32 (hostmem.device_ptr of a page-locked host
-        array) that also receives offs[i, nb] (so_pack_frames_ex)."""
+        array) that also receives offs[i, nb] (so_pack_frames_ex).
+        coding: "varint" (so_pack_frames_ex) or "bits" (so_pack_frames_bits: Exp-Golomb codes,
+        about half the bytes; bitstream.unpack_frame_bits decodes it)."""
+        bits = pack_coding_is_bits(coding)
         n = len(syms)
         if n == 0:
             raise ValueError("pack_symbols: no frames")
         nb = syms[0].split.numel()
         if any(s.split.numel() != nb for s in syms):
             raise ValueError("pack_symbols: frames with different block counts")
-        cap = self.pack_bound(nb) if out is None else out.shape[1]
+        cap = self.pack_bound(nb, coding) if out is None else out.shape[1]
         offs = torch.empty((n, nb + 1), dtype=torch.int32, device=self.device) if offs is None else offs
         out = torch.empty((n, cap), dtype=torch.uint8, device=self.device) if out is None else out
         if offs.shape != (n, nb + 1) or offs.dtype != torch.int32 or out.shape[0] != n or out.dtype != torch.uint8:
@@ -615,16 +626,19 @@ class Engine:
         def arr(ts):
             return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
         types = (ctypes.c_int32 * n)(*[int(s.frame_type) for s in syms])
-        rc = self.lib.so_pack_frames_ex(n, types, arr([s.split for s in syms]), arr([s.mv for s in syms]),
-                                        arr([s.qtc for s in syms]), nb, self.bs, arr(list(offs)), arr(list(out)),
-                                        int(cap), totals_ptr, _lib.stream_handle(self.device))
-        _lib.check(rc, "so_pack_frames")
+        pack = self.lib.so_pack_frames_bits if bits else self.lib.so_pack_frames_ex
+        rc = pack(n, types, arr([s.split for s in syms]), arr([s.mv for s in syms]),
+                  arr([s.qtc for s in syms]), nb, self.bs, arr(list(offs)), arr(list(out)),
+                  int(cap), totals_ptr, _lib.stream_handle(self.device))
+        _lib.check(rc, "so_pack_frames_bits" if bits else "so_pack_frames")
         return offs, out
 
-    def unpack_symbols(self, frame_types: list, packed: list, offs: list) -> list:
-        """so_unpack_frames: packed streams (device uint8) + their block offsets (device int32
-        [nb + 1], as pack_symbols wrote them) -> FrameSymbols with split / mv / qtc (no recon,
-        tokens or metrics).  Raises ValueError on a malformed stream (synchronises once)."""
+    def unpack_symbols(self, frame_types: list, packed: list, offs: list, coding: str = "varint") -> list:
+        """so_unpack_frames (coding "varint") or so_unpack_frames_bits ("bits"): packed streams
+        (device uint8) + their block offsets (device int32 [nb + 1], as pack_symbols wrote them)
+        -> FrameSymbols with split / mv / qtc (no recon, tokens or metrics).  Raises ValueError
+        on a malformed stream (synchronises once)."""
+        name = "so_unpack_frames_bits" if pack_coding_is_bits(coding) else "so_unpack_frames"
         n = len(packed)
         syms = [self.new_symbols(int(t)) for t in frame_types]
         err = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -632,13 +646,13 @@ class Engine:
         def arr(ts):
             return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
         types = (ctypes.c_int32 * n)(*[int(t) for t in frame_types])
-        rc = self.lib.so_unpack_frames(n, types, arr(packed), arr(offs), self.nb, self.bs, arr([s.split for s in syms]),
-                                       arr([s.mv for s in syms]), arr([s.qtc for s in syms]), err.data_ptr(),
-                                       _lib.stream_handle(self.device))
-        _lib.check(rc, "so_unpack_frames")
+        rc = getattr(self.lib, name)(n, types, arr(packed), arr(offs), self.nb, self.bs, arr([s.split for s in syms]),
+                                     arr([s.mv for s in syms]), arr([s.qtc for s in syms]), err.data_ptr(),
+                                     _lib.stream_handle(self.device))
+        _lib.check(rc, name)
         bad = int(err.item())
         if bad:
-            raise ValueError(f"so_unpack_frames: malformed packed stream at block {bad - 1}")
+            raise ValueError(f"{name}: malformed packed stream at block {bad - 1}")
         return syms
 
     # ---- metrics ---------------------------------------------------------------------------

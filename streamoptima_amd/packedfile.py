@@ -2,11 +2,12 @@
 the reference's two text files (transmit_bitstream, Encoder.py:1544-1573; decode_bitstream,
 decoder.py:686-709).
 
-    header   b"SOPK" | u32 version 1 | u32 H | u32 W | u32 bs | u32 nframes | u32 nb
+    header   b"SOPK" | u32 version | u32 H | u32 W | u32 bs | u32 nframes | u32 nb
     frame    u8 frame_type | u16 nqp | i8 qp[nqp] (per-row QPs under rate control, else 0)
              | u32 nbytes | u16 block_bytes[nb] | bytes[nbytes]
 
-Little endian.  block_bytes lets the GPU decoder (so_unpack_frames) start every block in
+Little endian.  Version 1 holds the varint coding of the stream (so_pack_frames), version 2
+the "bits" coding (so_pack_frames_bits) in the same layout.  block_bytes lets the GPU decoder (so_unpack_frames) start every block in
 parallel: the offsets are their exclusive prefix sums.  Per-block QP maps (ROI / two-pass RC)
 are not carried: such GOPs use the text bitstream.
 """
@@ -17,18 +18,22 @@ import struct
 import numpy as np
 import torch
 
-MAGIC, VERSION = b"SOPK", 1
+MAGIC = b"SOPK"
+VERSIONS = {"varint": 1, "bits": 2}              # the stream's coding -> container version
 
 
-def write(path: str, eng, symbols: list, qp_rows: list | None = None) -> int:
-    """Pack `symbols` (FrameSymbols on the device) and write the container; returns its size."""
+def write(path: str, eng, symbols: list, qp_rows: list | None = None, coding: str = "varint") -> int:
+    """Pack `symbols` (FrameSymbols on the device) in `coding` ("varint" or "bits") and write
+    the container; returns its size."""
+    if coding not in VERSIONS:
+        raise ValueError(f"packed stream coding {coding!r} (\"varint\" or \"bits\")")
     if any(s.extra.get("qp_map") is not None for s in symbols):
         raise NotImplementedError("per-block QP maps (ROI / two-pass RC) are not carried by the packed container")
-    offs, out = eng.pack_symbols(symbols)
+    offs, out = eng.pack_symbols(symbols, coding=coding)
     offs_h = offs.cpu().numpy().astype(np.int64)
     size = 0
     with open(path, "wb") as f:
-        hdr = MAGIC + struct.pack("<6I", VERSION, eng.h, eng.w, eng.bs, len(symbols), eng.nb)
+        hdr = MAGIC + struct.pack("<6I", VERSIONS[coding], eng.h, eng.w, eng.bs, len(symbols), eng.nb)
         f.write(hdr)
         size += len(hdr)
         for i, s in enumerate(symbols):
@@ -43,14 +48,15 @@ def write(path: str, eng, symbols: list, qp_rows: list | None = None) -> int:
 
 
 def read(path: str, device) -> dict:
-    """-> {"h", "w", "bs", "nb", "frame_types", "qp_rows", "packed": [device uint8],
-    "offs": [device int32 [nb + 1]]}."""
+    """-> {"h", "w", "bs", "nb", "coding", "frame_types", "qp_rows", "packed": [device uint8],
+    "offs": [device int32 [nb + 1]]}; "coding" is "varint" (version 1) or "bits" (version 2)."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:4] != MAGIC:
         raise ValueError(f"{path}: not a packed StreamOptima bitstream")
     version, h, w, bs, nframes, nb = struct.unpack_from("<6I", data, 4)
-    if version != VERSION:
+    coding = {v: c for c, v in VERSIONS.items()}.get(version)
+    if coding is None:
         raise ValueError(f"{path}: container version {version}")
     p = 4 + 24
     fts, qps, packed, offs = [], [], [], []
@@ -73,4 +79,4 @@ def read(path: str, device) -> dict:
         p += nbytes
     if p != len(data):
         raise ValueError(f"{path}: {len(data) - p} bytes after the last frame")
-    return {"h": h, "w": w, "bs": bs, "nb": nb, "frame_types": fts, "qp_rows": qps, "packed": packed, "offs": offs}
+    return {"h": h, "w": w, "bs": bs, "nb": nb, "coding": coding, "frame_types": fts, "qp_rows": qps, "packed": packed, "offs": offs}
