@@ -202,6 +202,10 @@ int so_get_option(int option);
  * dense SADs), summed like word 64.  The dense-equivalent count of the reference's full scan
  * (Encoder.py:688-715) is (valid candidates) x 256 per P-frame; this is what ran. */
 #define SO_P_RUN_SAD_OPS_WORD 66
+/* Words 68, 69: wavefronts (four blocks each) of the plain one-GPU run whose fast forward /
+ * inverse transform could not certify a rounding and re-ran the pocketfft sequence, summed like
+ * word 64 (a content statistic: exact ties of the rational coefficients, low QPs). */
+#define SO_P_RUN_TQ_FALLBACK_WORD 68
 /* Wait health, accumulated like the timeout count ("Waits"):
  * word 33: waits whose relaxed flag polls kept missing a flag for 1 ms of polling that an
  *          atomic read then found set (the wait completes with atomic reads; not an error);

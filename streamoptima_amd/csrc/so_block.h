@@ -247,6 +247,58 @@ SO_DEV void xform2d_rows_dw(double* lds, int l, const int* in_row, double* out_r
     wave_sync();   // lds free for reuse
 }
 
+// The 16 x 16 transform of integer rows with the fast passes of so_dct.h (dct2_16_fast /
+// dct3_16_fast): within dct::kFastBoundFwd / kFastBoundInv of the real transform, not
+// pocketfft's bits -- the caller certifies every rounding and falls back to xform2d_rows_dw /
+// xform2d_rows (tq16_exact).  The same scratch and transposes as those: DW = the 16 x 17 dword
+// buffer in two rounds behind two LDS base addresses, else 16 x 17 doubles.
+template <bool INVERSE, bool DW, class FT>
+SO_DEV void xform2d_fast(double* lds, int l, const int* in_row, double (&v)[16], const FT& ft) {
+    constexpr int N = 16, P = N + 1;
+    typedef __attribute__((address_space(3))) uint32_t* lds_u32p;
+    lds_u32p rowp = (lds_u32p)(reinterpret_cast<uint32_t*>(lds) + l * P);
+    lds_u32p colp = (lds_u32p)(reinterpret_cast<uint32_t*>(lds) + l);
+    if constexpr (DW) asm volatile("" : "+v"(rowp), "+v"(colp));
+    {
+#pragma unroll
+        for (int c = 0; c < N; ++c) rowp[c] = (uint32_t)in_row[c];
+        wave_sync();
+        int x[N];
+#pragma unroll
+        for (int r = 0; r < N; ++r) x[r] = (int)colp[r * P];
+        wave_sync();   // every lane's int reads before the values below overwrite them
+        if constexpr (INVERSE) {
+#pragma unroll
+            for (int r = 0; r < N; ++r) v[r] = (double)x[r];
+            dct::dct3_16_fast(v, ft);
+        } else {
+            dct::dct2_16_fast_i(x, v, ft);
+        }
+    }
+    if constexpr (DW) {
+        uint32_t lo[N];
+#pragma unroll
+        for (int r = 0; r < N; ++r) colp[r * P] = (uint32_t)__builtin_bit_cast(uint64_t, v[r]);
+        wave_sync();
+#pragma unroll
+        for (int c = 0; c < N; ++c) lo[c] = rowp[c];
+        wave_sync();   // every lane's low dwords read before the high ones overwrite them
+#pragma unroll
+        for (int r = 0; r < N; ++r) colp[r * P] = (uint32_t)(__builtin_bit_cast(uint64_t, v[r]) >> 32);
+        wave_sync();
+#pragma unroll
+        for (int c = 0; c < N; ++c) v[c] = __builtin_bit_cast(double, ((uint64_t)rowp[c] << 32) | (uint64_t)lo[c]);
+    } else {
+#pragma unroll
+        for (int r = 0; r < N; ++r) lds[r * P + l] = v[r];
+        wave_sync();
+#pragma unroll
+        for (int c = 0; c < N; ++c) v[c] = lds[l * P + c];
+    }
+    if constexpr (INVERSE) dct::dct3_16_fast(v, ft); else dct::dct2_16_fast(v, ft);
+    wave_sync();   // lds free for reuse
+}
+
 // The forward xform2d_rows<16, false> of integer rows through half its LDS (16 x 9 doubles): the
 // int32 transpose fits the scratch whole (16 x 17 words), the FP64 one goes back to rows in two
 // halves (as xform2d_rows_half).  The same operations as xform2d_rows bit for bit (the column

@@ -79,6 +79,11 @@ static __constant__ double kTw16Tab[45] = {
 #undef SO_TW_D
 #undef SO_TW_H
 typedef const __attribute__((address_space(4))) double* so_cdp;
+#if defined(__HIP_DEVICE_COMPILE__)
+#define SO_SGPR_BARRIER(q) asm volatile("" : "+s"(q))
+#else   // host builds of this header (tools/check_dct_*.cpp): no such register class
+#define SO_SGPR_BARRIER(q) (void)(q)
+#endif
 struct TW16R {
     so_cdp p;
     SO_DEV double dct(int i) const { return p[i]; }
@@ -92,7 +97,7 @@ struct TW16R {
 };
 SO_DEV TW16R tw16_table() {
     so_cdp q = (so_cdp)kTw16Tab;
-    asm volatile("" : "+s"(q));
+    SO_SGPR_BARRIER(q);
     return TW16R{q};
 }
 // The same for N = 8 (the VBS sub-blocks).
@@ -114,7 +119,7 @@ struct TW8R {
 };
 SO_DEV TW8R tw8_table() {
     so_cdp q = (so_cdp)kTw8Tab;
-    asm volatile("" : "+s"(q));
+    SO_SGPR_BARRIER(q);
     return TW8R{q};
 }
 
@@ -559,6 +564,193 @@ SO_DEV void dct3_8_i(const int (&x)[8], double (&c)[8], const TW& tw = TW{}) {
 
 #undef SO_PM
 #undef SO_MULPM
+
+// ---- fast 16-point transforms (the plain persistent run, SO_TQ_FAST) -------------------------
+// dct2_16_fast / dct3_16_fast: the orthonormal DCT-II / DCT-III of one lane's vector, about 95
+// FP64 operations against pocketfft's ~165, NOT bit-identical to it: the caller certifies that
+// the integer it rounds to is the one pocketfft's value rounds to and re-runs the sequence above
+// where it cannot (so_block.h, xform2d_fast and the rules in tq16_exact).
+//
+// With a_i = x_i + x_15-i, b_i = x_i - x_15-i the even outputs are the 8-point DCT-II of a (split
+// once more: X0, X8 = (e0 +- e1) / 4 exactly, X4, X12 a rotation, X2..X14 a 4 x 4 matrix) and the
+// odd ones the 8-point DCT-IV of b.  The DCT-IV uses 2 cos(t) cos(2k t) = cos((2k+1) t) +
+// cos((2k-1) t): with u_n = b_n s cos(pi (2n+1) / 32) (s = sqrt(1/8)) and T the unnormalised
+// 8-point DCT-II of u, y_0 = T_0 and y_k = 2 T_k - y_k-1; every 2 T_k is a chain of FMAs seeded
+// with -y_k-1, so the recursion costs no operation of its own.  The DCT-III is the transposed
+// graph (the DCT-IV matrix is symmetric).  All normalisation is folded into the constants.
+//
+// Error bounds (u = 2^-53, constants correctly rounded, FMA rounds once).  A computed output
+// differs from the real one by at most gamma_L A, gamma_L = L u / (1 - L u), where L is the
+// largest number of roundings (operations and constants) on a path from an input to an output and
+// A is the output of the same graph with every constant and input replaced by its magnitude and
+// every subtraction by an addition (the standard path-sum bound).  For inputs |x_n| <= M:
+//   fast:      L <= 28 (5 to the DCT-IV's inner butterflies, 22 along the y_1..y_7 chain, 1);
+//              A <= 36.63 M (DCT-II), 20.18 M (DCT-III)  -- the graphs evaluated on all ones;
+//   pocketfft: L <= 16; A <= 2 x 5.66 x 4 x 0.1768 x 1.415 M <= 11.4 M (dct2: prelude, radb4<4,1>,
+//              radb4<1,4>, fct, post-twiddles), 2.83 x 4 x 5.66 x 0.1768 x 2 M <= 22.7 M (dct3).
+// 2-D, pass 2 on pass 1's outputs, whose own error E1 is carried over by the real transform
+// (sum_n |C_kn| <= 4):  E <= gamma_L A(M2) + 4 E1.
+//   forward, residuals |r| <= 255: M = 255, M2 <= 4 x 255 = 1020:
+//              fast  3.11e-15 x 36.63 x (1020 + 4 x 255) = 2.33e-10, pocketfft 1.78e-15 x 11.4 x 2040 = 4.14e-11;
+//   inverse, dequantised levels: a level is non-zero only if |TC| >= 2^(k-1), so |dq| <= 2 |TC|,
+//              and ||TC||_2 <= ||r||_2 + 8 <= 4088 (Parseval; rint moves each of 256 values by 1/2):
+//              M = 2^13, and every pass-1 output is at most its column's norm, M2 <= 2^13:
+//              fast  3.11e-15 x 20.18 x 5 x 8192 = 2.57e-9, pocketfft 1.78e-15 x 22.7 x 5 x 8192 = 1.66e-9.
+// The flag thresholds are the sums of the two bounds of a direction with a margin:
+//   forward  kFastDeltaFwd = 2^-30 = 9.31e-10 >= 3.3 x (2.33e-10 + 4.14e-11);
+//   inverse  kFastDeltaInv = 1.5 x 2^-24 = 8.94e-8 >= 21 x (2.57e-9 + 1.66e-9): the inverse rule
+//            is evaluated on a 2^-24 fixed-point grid (tq16_exact), which sets this value.
+constexpr double kFastBoundFwd = 2.33e-10, kPocketBoundFwd = 4.14e-11;
+constexpr double kFastBoundInv = 2.57e-9, kPocketBoundInv = 1.66e-9;
+constexpr double kFastDeltaFwd = 0x1.0p-30, kFastDeltaInv = 0x1.8p-24;
+static_assert(kFastDeltaFwd >= kFastBoundFwd + kPocketBoundFwd && kFastDeltaInv >= kFastBoundInv + kPocketBoundInv,
+              "a flag threshold below the sum of the two error bounds");
+
+// [0] 1/4, [1..2] s cos(pi/8), s cos(3 pi/8), [3..6] s cos((2m+1) pi/16), [7..14] s cos((2n+1) pi/32),
+// [15] sqrt 2, [16..17] 2 cos(pi/8), 2 cos(3 pi/8), [18..21] 2 cos((2m+1) pi/16)
+#define SO_FAST16_CONSTANTS                                                                        \
+    0x1.0000000000000p-2, 0x1.4e7ae9144f0fcp-2, 0x1.1517a7bdb3895p-3, 0x1.63150b15e8536p-2,        \
+    0x1.2d062ef88e319p-2, 0x1.92469c0dcf32dp-3, 0x1.1a855dec071b5p-4, 0x1.684b9c80f1a8bp-2,        \
+    0x1.5a730c6c21c67p-2, 0x1.3f4a237187eafp-2, 0x1.17dc13dab2dd6p-2, 0x1.cb598cc4beea0p-3,        \
+    0x1.5553e3f5b5e58p-3, 0x1.a4608aafa8527p-4, 0x1.1be35182fe5aap-5, 0x1.6a09e667f3bcdp+0,        \
+    0x1.d906bcf328d46p+0, 0x1.87de2a6aea963p-1, 0x1.f6297cff75cb0p+0, 0x1.a9b66290ea1a3p+0,        \
+    0x1.1c73b39ae68c8p+0, 0x1.8f8b83c69a60bp-2
+constexpr double kFast16[22] = {SO_FAST16_CONSTANTS};
+static __constant__ double kFast16Tab[22] = {SO_FAST16_CONSTANTS};
+#undef SO_FAST16_CONSTANTS
+struct FT16 {    // literals
+    SO_DEV double k(int i) const { return kFast16[i]; }
+};
+struct FT16R {   // scalar loads from the constant table, as TW16R
+    so_cdp p;
+    SO_DEV double k(int i) const { return p[i]; }
+};
+SO_DEV FT16R ft16_table() {
+    so_cdp q = (so_cdp)kFast16Tab;
+    SO_SGPR_BARRIER(q);
+    return FT16R{q};
+}
+
+// +-cos(pi q / 16), q odd, as a signed entry of the table's four magnitudes at `base`
+template <class FT>
+SO_DEV double fast_c16(const FT& t, int base, int q) {
+    q &= 31;
+    if (q > 16) q = 32 - q;
+    const bool neg = q > 8;
+    if (neg) q = 16 - q;
+    const double c = t.k(base + (q - 1) / 2);
+    return neg ? -c : c;
+}
+
+// the 8-point DCT-IV scaled by s: y_j = s sum_n b_n cos(pi (2n+1)(2j+1) / 32)
+template <class FT>
+SO_DEV void dct4_8_fast(const double (&b)[8], double (&y)[8], const FT& t) {
+    double u[8], ap[4], bp[4];
+#pragma unroll
+    for (int n = 0; n < 8; ++n) u[n] = b[n] * t.k(7 + n);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        ap[i] = u[i] + u[7 - i];
+        bp[i] = u[i] - u[7 - i];
+    }
+    const double e0 = ap[0] + ap[3], e1 = ap[1] + ap[2], f0 = ap[0] - ap[3], f1 = ap[1] - ap[2];
+    y[0] = e0 + e1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double acc = -y[2 * j];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc = __builtin_fma(fast_c16(t, 18, (2 * i + 1) * (2 * j + 1)), bp[i], acc);
+        y[2 * j + 1] = acc;
+        if (j == 0) y[2] = __builtin_fma(t.k(17), f1, __builtin_fma(t.k(16), f0, -acc));
+        if (j == 1) y[4] = __builtin_fma(t.k(15), e0 - e1, -acc);
+        if (j == 2) y[6] = __builtin_fma(-t.k(16), f1, __builtin_fma(t.k(17), f0, -acc));
+    }
+}
+
+// the outputs of dct2_16_fast from the two butterfly stages' results: cc = the four sums of the
+// second stage as e0, e1, f0, f1; d its differences; b the first stage's differences
+template <class FT>
+SO_DEV void dct2_16_fast_tail(double e0pe1, double e0me1, double f0, double f1, const double (&d)[4],
+                              const double (&b)[8], double (&c)[16], const FT& t) {
+    c[0] = e0pe1 * t.k(0);
+    c[8] = e0me1 * t.k(0);
+    c[4] = __builtin_fma(t.k(2), f1, t.k(1) * f0);
+    c[12] = __builtin_fma(-t.k(1), f1, t.k(2) * f0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double acc = fast_c16(t, 3, 2 * j + 1) * d[0];
+#pragma unroll
+        for (int i = 1; i < 4; ++i) acc = __builtin_fma(fast_c16(t, 3, (2 * i + 1) * (2 * j + 1)), d[i], acc);
+        c[4 * j + 2] = acc;
+    }
+    double y[8];
+    dct4_8_fast(b, y, t);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) c[2 * j + 1] = y[j];
+}
+
+template <class FT = FT16>
+SO_DEV void dct2_16_fast(double (&c)[16], const FT& t = FT{}) {
+    double a[8], b[8], cc[4], d[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        a[i] = c[i] + c[15 - i];
+        b[i] = c[i] - c[15 - i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        cc[i] = a[i] + a[7 - i];
+        d[i] = a[i] - a[7 - i];
+    }
+    const double e0 = cc[0] + cc[3], e1 = cc[1] + cc[2];
+    dct2_16_fast_tail(e0 + e1, e0 - e1, cc[0] - cc[3], cc[1] - cc[2], d, b, c, t);
+}
+
+// the same on integers (the first pass of the 2-D forward: residuals): the butterflies are exact
+// in int32 (|sums| <= 16 x 255), converted where they first meet a constant
+template <class FT = FT16>
+SO_DEV void dct2_16_fast_i(const int (&x)[16], double (&c)[16], const FT& t = FT{}) {
+    int a[8], cc[4];
+    double b[8], d[4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        a[i] = x[i] + x[15 - i];
+        b[i] = (double)(x[i] - x[15 - i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        cc[i] = a[i] + a[7 - i];
+        d[i] = (double)(a[i] - a[7 - i]);
+    }
+    const int e0 = cc[0] + cc[3], e1 = cc[1] + cc[2];
+    dct2_16_fast_tail((double)(e0 + e1), (double)(e0 - e1), (double)(cc[0] - cc[3]), (double)(cc[1] - cc[2]), d, b,
+                      c, t);
+}
+
+template <class FT = FT16>
+SO_DEV void dct3_16_fast(double (&c)[16], const FT& t = FT{}) {
+    const double p = t.k(0) * c[0];
+    const double e0 = __builtin_fma(t.k(0), c[8], p), e1 = __builtin_fma(-t.k(0), c[8], p);
+    const double f0 = __builtin_fma(t.k(2), c[12], t.k(1) * c[4]), f1 = __builtin_fma(-t.k(1), c[12], t.k(2) * c[4]);
+    const double cc[4] = {e0 + f0, e1 + f1, e1 - f1, e0 - f0};
+    double a[8], xo[8], bo[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double acc = fast_c16(t, 3, 2 * i + 1) * c[2];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) acc = __builtin_fma(fast_c16(t, 3, (2 * i + 1) * (2 * j + 1)), c[4 * j + 2], acc);
+        a[i] = cc[i] + acc;
+        a[7 - i] = cc[i] - acc;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xo[j] = c[2 * j + 1];
+    dct4_8_fast(xo, bo, t);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        c[i] = a[i] + bo[i];
+        c[15 - i] = a[i] - bo[i];
+    }
+}
 
 }  // namespace dct
 }  // namespace so

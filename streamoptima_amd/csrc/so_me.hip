@@ -721,7 +721,7 @@ extern "C" int so_debug_set_run_stamps(void* p) {
     X(poll_iter) X(stage_win) X(stage_win_int) X(stage_win_edge) X(dense_tile) X(dense_tile_block) X(byte_sums) \
     X(block_top) X(bound) X(umin) X(umin_edge) X(ballots) X(bal_row) X(dense_fallback) X(survivors) X(sur_one) X(sur_le4) X(sur_pass) \
     X(search_end) X(decode_keys) X(tq_residual) X(tq_fwd) X(tq_quant) X(tq_tokens) X(tq_qtc_store) X(tq_inv) \
-    X(tq_recon) X(tq_sse_records) X(post) X(done_flag) X(task_end) X(vbs_block) X(vbs_umin) X(vbs_list_a) \
+    X(tq_recon) X(tq_fwd_near) X(tq_fwd_fallback) X(tq_inv_fallback) X(tq_sse_records) X(post) X(done_flag) X(task_end) X(vbs_block) X(vbs_umin) X(vbs_list_a) \
     X(vbs_pass) X(vbs_list_b) X(vbs_final) X(vbs_dense) X(vbs_fwd) X(vbs_fwd_sub) X(vbs_final_q) X(vbs_inv) \
     X(vbs_inv_split) X(vbs_inv_end) X(wait_w0) X(keys_tail) X(p1_tq) X(p1_flag) X(p2_wait) X(p2_sums) X(p2_tq) \
     X(p2_flag)
@@ -1874,7 +1874,8 @@ struct PTileLds {
     unsigned long long keys[NU];
     uint32_t st[3];
     MeRec mer[NU];                         // decoded ME records (dx, dy, ref, sad)
-    int32_t msum[G::TBY];                  // two-pass runs: pass-1 token sum of each block row
+    int32_t msum[G::TBY];                  // two-pass runs: pass-1 token sum of each block row (the plain
+                                           // one-GPU run: [0], [1] count its transform fallbacks)
     uint32_t fwd_flags;                    // fwd_mfma: blocks whose levels need the FP64 forward
     alignas(16) double un[VBS ? PTileGeoVbs<G>::U64 : PTileGeo<G, HALFTQ>::U64];   // byte sums + survivor lists | FP64 transposes
     // VBS: each block's split state (0 block, 1 split, 2 none) between tq16_vbs_fwd and
@@ -1907,7 +1908,21 @@ struct PHalo {
 #define SO_TQ_TW8() dct::tw8_table()
 #endif
 // ZSKIP (SO_OPT_RUN_ZERO_SKIP): a wave whose four blocks all quantised to zero skips the IDCT
-template <class G, bool SC1, bool HALO = false, bool TOK = false, bool HALFTQ = false, bool ZSKIP = false>
+// FAST (SO_TQ_FAST, the plain one-GPU run): both 2-D transforms by the fast passes of so_dct.h
+// (xform2d_fast), each with a certificate and the pocketfft sequence as the wave's fallback:
+//  * forward: z flagged if ||z - rint(z)| - 1/2| <= kFastDeltaFwd and the integer on z's other
+//    side of that half quantises to another level (at k = 0 it always does);
+//  * inverse: a pixel flagged if its value lies within kFastDeltaInv of a half-integer, tested
+//    on the 2^-24 fixed-point image of the value that also yields the rounded pixel;
+//  * one ballot per direction: a wave with a flagged lane re-runs that transform with
+//    xform2d_rows_dw / xform2d_rows from the rows still in LDS (the levels from the row it
+//    stored) and counts itself in S.msum[0] / [1] (two-pass words, unused by this run).
+#ifndef SO_TQ_FAST
+#define SO_TQ_FAST 1
+#endif
+#define SO_TQ_FT() dct::ft16_table()
+template <class G, bool SC1, bool HALO = false, bool TOK = false, bool HALFTQ = false, bool ZSKIP = false,
+          bool FAST = false>
 SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scratch, int bx0, int byt0, int nbx, int by0, int by1,
                        int W, int qp_rd, const int32_t* __restrict__ qp_row, const int32_t* __restrict__ qp_map,
                        const PFrameOut& o, const PHalo& hl = PHalo{}, bool qs = false) {
@@ -1915,8 +1930,8 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
     const int bxl = g % TBX, byl = g / TBX;
     const int gbx = bx0 + bxl, gby = byt0 + byl;
     if (gbx < nbx && gby < by1) {   // uniform over the block's 16 lanes
-        const size_t b = (size_t)(gby - by0) * nbx + gbx;
-        const int x = gbx * 16, y = gby * 16;
+        size_t b = (size_t)(gby - by0) * nbx + gbx;
+        int x = gbx * 16, y = gby * 16;
         const int qpr = qp_map ? qp_map[(size_t)gby * nbx + gbx] : (qp_row ? qp_row[gby] : qp_rd);
         const int dx = S.mer[g][0], dy = S.mer[g][1], rf = S.mer[g][2], sad = S.mer[g][3];
         const int prow = byl * 16 + SR + dy + l, pcol = bxl * 16 + SR + dx;   // window coordinates
@@ -1926,6 +1941,30 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
         // integer half-to-even, held in the low mantissa dword as two's complement -- one
         // v_add_f64 instead of v_rndne + v_cvt_i32
         constexpr double kRne = 0x1.8p52;
+        // FAST: the prediction and current rows re-derived from the block and lane numbers where a
+        // rare path or the reconstruction needs them again (held across the transforms they were
+        // spilled, as the record and row address below)
+        // and so are the block's index, position and scratch after each transform: nothing but g
+        // and l then lives through it
+        const auto derive = [&]() {
+            if constexpr (FAST) {
+                asm volatile("" : "+v"(g), "+v"(l));
+                const int gbx2 = bx0 + g % TBX, gby2 = byt0 + g / TBX;
+                b = (size_t)(gby2 - by0) * nbx + gbx2;
+                x = gbx2 * 16;
+                y = gby2 * 16;
+                dl = S.un + g * tq_scratch<G, HALFTQ>();
+            }
+        };
+        const auto rows_of = [&](int g2, int l2, int& prow2, int& pcol2, const uint32_t*& crow2) {
+            asm volatile("" : "+v"(g2), "+v"(l2));
+            const int bxl2 = g2 % TBX, byl2 = g2 / TBX;
+            lds_vu32p mp = (lds_vu32p)reinterpret_cast<const uint32_t*>(&S.mer[g2]);
+            const uint32_t w0 = mp[0];
+            prow2 = byl2 * 16 + SR + ((int)w0 >> 16) + l2;
+            pcol2 = bxl2 * 16 + SR + (int)(int16_t)(w0 & 0xFFFFu);
+            crow2 = S.curt + (byl2 * 16 + l2) * G::CPD + bxl2 * 4;
+        };
         int q[16];
         if (qs) {
             const so_v4u* qr = reinterpret_cast<const so_v4u*>(reinterpret_cast<const int16_t*>(dl) + l * 16);
@@ -1941,20 +1980,92 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
         } else {
             SO_MARK(tq_residual);
             int res[16];
-            {
+            const auto load_res = [&](int prow_, int pcol_, const uint32_t* crow_) {
                 uint32_t pw[4];
-                win_row16<G::RP>(S.win, prow, pcol, pw);
+                win_row16<G::RP>(S.win, prow_, pcol_, pw);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const uint32_t cw = crow[k];
+                    const uint32_t cw = crow_[k];
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
                         res[4 * k + e] = (int)((cw >> (8 * e)) & 255) - (int)((pw[k] >> (8 * e)) & 255);
                 }
-            }
+            };
+            load_res(prow, pcol, crow);
             double tcr[16];
             SO_MARK(tq_fwd);
             static_assert(!HALFTQ || TOK, "the half scratch carries the forward transform only");
+            static_assert(!FAST || (!HALFTQ && !TOK && !HALO), "the fast transforms: the plain run only");
+            // 2^-k as a double's high dword, k = qp + e(l + c): coefficient c + 1 of lane l has the
+            // exponent of coefficient c of lane l + 1 (DPP row_shl:1; lane 15 is past the
+            // anti-diagonal from c = 1 on), so a lane's exponents cost one move per coefficient
+            const int sc_hi2 = (1023 - 2 - qpr) << 20;
+            const auto quant_fma = [&](bool certify) -> bool {
+                int sc_hi = (1023 - qpr - (l == 15 ? 1 : 0)) << 20;
+                bool flag = false;
+#pragma unroll
+                for (int c0 = 0; c0 < 16; c0 += 4) {   // four coefficients, then one uniform branch
+                    uint64_t nm[4], any = 0;   // per coefficient: the lanes whose value is near a half
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int c = c0 + j;
+                        const double sc = __builtin_bit_cast(double, (uint64_t)(uint32_t)sc_hi << 32);
+                        const double r = __builtin_rint(tcr[c]);
+                        q[c] = (int)(uint32_t)__builtin_bit_cast(uint64_t, __builtin_fma(r, sc, kRne));
+                        if (certify) {
+                            nm[j] = __builtin_amdgcn_ballot_w64(__builtin_fabs(tcr[c] - r) >= 0.5 - dct::kFastDeltaFwd);
+                            any |= nm[j];
+                        }
+                        if (c < 15) sc_hi = __builtin_amdgcn_update_dpp(sc_hi2, sc_hi, 0x101, 0xF, 0xF, false);
+                    }
+#ifdef SO_TQ_CENSUS_NO_NEAR   // census builds: the path with no value near a half, by itself
+                    any = 0;
+#endif
+                    if (certify && any != 0) {
+                        // a value near a half (mostly the rational coefficients' exact ties): flagged
+                        // if the integer on its other side quantises to another level
+                        SO_MARK(tq_fwd_near);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            if (nm[j] != 0) {   // uniform
+                                const int c = c0 + j;
+                                const double sc = __builtin_bit_cast(
+                                    double, (uint64_t)(uint32_t)((1023 - q_exp_fast<16>(l, c, qpr)) << 20) << 32);
+                                const double r = __builtin_rint(tcr[c]), d = tcr[c] - r;   // d: exact
+                                const double r2 = r + __builtin_copysign(1.0, d);
+                                const int q2 = (int)(uint32_t)__builtin_bit_cast(uint64_t, __builtin_fma(r2, sc, kRne));
+                                flag |= __builtin_fabs(d) >= 0.5 - dct::kFastDeltaFwd && q2 != q[c];
+                            }
+                        }
+                        SO_MARK(tq_quant);
+                    }
+                }
+                return certify && __builtin_amdgcn_ballot_w64(flag) != 0;
+            };
+            if constexpr (FAST) {
+                xform2d_fast<false, G::TQDW>(dl, l, res, tcr, SO_TQ_FT());
+                // the whole transform before the quantiser's branches (its tail sunk into them held
+                // the pass's intermediates through all of them)
+                asm volatile("" : "+v"(tcr[0]), "+v"(tcr[1]), "+v"(tcr[2]), "+v"(tcr[3]), "+v"(tcr[4]), "+v"(tcr[5]),
+                             "+v"(tcr[6]), "+v"(tcr[7]));
+                asm volatile("" : "+v"(tcr[8]), "+v"(tcr[9]), "+v"(tcr[10]), "+v"(tcr[11]), "+v"(tcr[12]), "+v"(tcr[13]),
+                             "+v"(tcr[14]), "+v"(tcr[15]));
+                SO_MARK(tq_quant);
+                if (quant_fma(true)) {
+                    SO_MARK(tq_fwd_fallback);
+                    const uint64_t act = __builtin_amdgcn_ballot_w64(true);
+                    if ((int)(threadIdx.x & 63) == __builtin_ctzll(act)) atomicAdd(reinterpret_cast<uint32_t*>(&S.msum[0]), 1u);
+                    int prow2, pcol2;
+                    const uint32_t* crow2;
+                    rows_of(g, l, prow2, pcol2, crow2);
+                    load_res(prow2, pcol2, crow2);
+                    if constexpr (G::TQDW)
+                        xform2d_rows_dw<false>(dl, l, res, tcr, SO_TQ_TW());
+                    else
+                        xform2d_rows<16, false>(dl, l, res, tcr, SO_TQ_TW());
+                    quant_fma(false);
+                }
+            } else {
             if constexpr (HALFTQ)
                 xform2d_fwd_i_half(dl, l, res, tcr, SO_TQ_TW());
             else if constexpr (G::TQDW)
@@ -1966,8 +2077,10 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
             for (int c = 0; c < 16; ++c)
                 q[c] = (int)(uint32_t)__builtin_bit_cast(
                     uint64_t, __builtin_amdgcn_ldexp(__builtin_rint(tcr[c]), -q_exp_fast<16>(l, c, qpr)) + kRne);
+            }
         }
         SO_MARK(tq_tokens);
+        derive();
         const int tok = block_tokens<16>(nullptr, l, q);
         if constexpr (TOK) {   // pass 1 of two-pass RC: the token count is all that is used
             if (l == 0) o.tokens[b] = tok;
@@ -2025,26 +2138,86 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
             }
             return e2;
         };
-        const auto full = [&]() -> int {   // dequantisation, IDCT, prediction + inverse
+        // dequantisation, the pocketfft IDCT, prediction + inverse
+        const auto full_exact = [&](const int (&ql)[16]) -> int {
             int dq[16];
             double rd[16];
-            dequant_row_int<16>(q, l, qpr, dq);
-            SO_MARK(tq_inv);
+            dequant_row_int<16>(ql, l, qpr, dq);
+            if constexpr (!FAST) SO_MARK(tq_inv);
             if constexpr (G::TQDW)
                 xform2d_rows_dw<true>(dl, l, dq, rd, SO_TQ_TW());
             else
                 xform2d_rows<16, true>(dl, l, dq, rd, SO_TQ_TW());
-            SO_MARK(tq_recon);
+            if constexpr (!FAST) SO_MARK(tq_recon);
+            derive();
             int rec[16];
             {
+                int prow2 = prow, pcol2 = pcol;
+                if constexpr (FAST) {
+                    const uint32_t* crow2;
+                    rows_of(g, l, prow2, pcol2, crow2);
+                }
                 uint32_t pw[4];
-                win_row16<G::RP>(S.win, prow, pcol, pw);
+                win_row16<G::RP>(S.win, prow2, pcol2, pw);
 #pragma unroll
                 for (int c = 0; c < 16; ++c)
                     rec[c] = (int)((pw[c >> 2] >> (8 * (c & 3))) & 255) +
                              (int)(uint32_t)__builtin_bit_cast(uint64_t, rd[c] + kRne);
             }
             return finish(rec);
+        };
+        const auto full = [&]() -> int {
+            if constexpr (FAST) {
+                {
+                    int dq[16], rec[16];
+                    double rd[16];
+                    {   // k = qp + e(l + c) by the same row shift as the quantiser's scale
+                        int k = qpr + (l == 15 ? 1 : 0);
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) {
+                            dq[c] = (int)((uint32_t)q[c] << k);
+                            if (c < 15) k = __builtin_amdgcn_update_dpp(qpr + 2, k, 0x101, 0xF, 0xF, false);
+                        }
+                    }
+                    SO_MARK(tq_inv);
+                    xform2d_fast<true, G::TQDW>(dl, l, dq, rd, SO_TQ_FT());
+                    asm volatile("" : "+v"(rd[0]), "+v"(rd[1]), "+v"(rd[2]), "+v"(rd[3]), "+v"(rd[4]), "+v"(rd[5]),
+                                 "+v"(rd[6]), "+v"(rd[7]));
+                    asm volatile("" : "+v"(rd[8]), "+v"(rd[9]), "+v"(rd[10]), "+v"(rd[11]), "+v"(rd[12]), "+v"(rd[13]),
+                                 "+v"(rd[14]), "+v"(rd[15]));
+                    SO_MARK(tq_recon);
+                    derive();
+                    // v + kFix holds round(v 2^24) + 2^23 in its low mantissa dword: bits 24.. are
+                    // floor(v + 1/2) (mod 256 with the prediction added above them: only rec & 255
+                    // is used), and the low 24 bits within 2 of 0 (mod 2^24) mean v is within
+                    // kFastDeltaInv = 1.5 x 2^-24 of a half-integer
+                    constexpr double kFix = 0x1.8p28 + 0.5;
+                    uint32_t mn = 0xFFFFFFFFu;
+                    {
+                        int prow2, pcol2;
+                        const uint32_t* crow2;
+                        rows_of(g, l, prow2, pcol2, crow2);
+                        uint32_t pw[4];
+                        win_row16<G::RP>(S.win, prow2, pcol2, pw);
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) {
+                            const uint32_t gfix = (uint32_t)__builtin_bit_cast(uint64_t, rd[c] + kFix);
+                            rec[c] = (int)(((((pw[c >> 2] >> (8 * (c & 3))) & 255u) << 24) + gfix) >> 24);
+                            const uint32_t t = (gfix + 2u) << 8;
+                            mn = t < mn ? t : mn;
+                        }
+                    }
+                    if (__builtin_amdgcn_ballot_w64(mn <= (4u << 8)) == 0) return finish(rec);
+                }
+                SO_MARK(tq_inv_fallback);
+                const uint64_t act = __builtin_amdgcn_ballot_w64(true);
+                if ((int)(threadIdx.x & 63) == __builtin_ctzll(act)) atomicAdd(reinterpret_cast<uint32_t*>(&S.msum[1]), 1u);
+                int qf[16];   // the levels this lane stored above (not held through the fast inverse)
+                load_row_i16<16>(o.qtc + b * 256 + l * 16, qf);
+                return full_exact(qf);
+            } else {
+                return full_exact(q);
+            }
         };
         int sse;
         if constexpr (ZSKIP) {
@@ -2563,7 +2736,7 @@ SO_DEV void store_sc1_i32(int32_t* p, int v) {
 }
 
 template <class G, bool SC1, class Pre = NoPre, bool HALO = false, bool TOK = false, bool VBS = false,
-          class Post = NoPre, bool HALFTQ = false, bool ZSKIP = false, int LISTS = 0>
+          class Post = NoPre, bool HALFTQ = false, bool ZSKIP = false, int LISTS = 0, bool FASTTQ = false>
 SO_DEV void ptile_body(PTileLds<G, VBS, HALFTQ>& S, int tile, const uint8_t* __restrict__ cur, const uint8_t* ref, int H, int W,
                        int by0, int by1, int qp_rd, const int32_t* __restrict__ qp_row,
                        const int32_t* __restrict__ qp_map, int32_t* __restrict__ out_best, const PFrameOut& o,
@@ -2655,7 +2828,7 @@ SO_DEV void ptile_body(PTileLds<G, VBS, HALFTQ>& S, int tile, const uint8_t* __r
                 tq16_vbs_fwd<G, SC1, HALO>(S, gq, ln & 15, S.un + gq * kTqScratchVbs, bx0, byt0, nbx, by0, by1, W, qp_rd,
                                            qp_row, qp_map, lam, o);
             else
-                tq16_exact<G, SC1, HALO, TOK, HALFTQ, ZSKIP>(S, gq, ln & 15, S.un + gq * tq_scratch<G, HALFTQ>(), bx0,
+                tq16_exact<G, SC1, HALO, TOK, HALFTQ, ZSKIP, FASTTQ>(S, gq, ln & 15, S.un + gq * tq_scratch<G, HALFTQ>(), bx0,
                                               byt0, nbx, by0, by1, W, qp_rd,
                                               qp_row, qp_map, o, hl, qs);
         }
@@ -2943,7 +3116,10 @@ constexpr int kRunTimeoutWord = SO_RUN_TIMEOUT_WORD, kRunDoneBase = SO_RUN_DONE_
 // it (SO_P_RUN_FALLBACK_WORD); each workgroup adds its total once, on its way out.  (Adding per
 // tile on the timeout word's line, which every waiting workgroup reads, cost +17 % per frame.)
 // [66..67] (same line, 64-bit): the search's executed SAD byte operations, added the same way.
+// [68], [69] (same line): waves of the plain run whose forward / inverse fast transform took the
+// pocketfft fallback (SO_P_RUN_TQ_FALLBACK_WORD), added the same way.
 constexpr int kRunExitWord = 1, kRunEpochWord = 2, kRunFallbackWord = 64, kRunSadOpsWord = SO_P_RUN_SAD_OPS_WORD;
+constexpr int kRunTqFallbackWord = SO_P_RUN_TQ_FALLBACK_WORD;
 // The waits' health words on the timeout word's line (written only when something unusual
 // happened, so the per-tile read of the timeout word stays a clean hit):
 //   [33] waits whose relaxed polls kept missing a flag that an atomic read then found set
@@ -3192,6 +3368,15 @@ SO_DEV void p_run_body(const PRunArgs& a, int nframes, const uint8_t* __restrict
     if (tid == 0) {                        // and its SAD byte operations
         s_fbsum = 0;
         s_ops = 0;
+    }
+    // the tall plain one-GPU run's transforms (tq16_exact's FAST): waves that took the forward /
+    // inverse fallback, counted in S.msum[0] / [1] over the workgroup's tasks.  The 32-row twins
+    // keep the pocketfft sequence: they run where a frame is a chain of tile steps, and there the
+    // fast passes' long dependent FMA chains cost more than their operation count saves (1080p
+    // GOP 0.673 against 0.629 ms with them)
+    constexpr bool kFastTq = SO_TQ_FAST != 0 && MODE == kRunSingle && !VBS && G::TBY == 3;
+    if constexpr (kFastTq) {
+        if (tid < 2) S.msum[tid] = 0;
     }
 #ifdef SO_MARKS_COUNT
     if (tid < 64) s_mark_cnt[tid] = 0u;   // visible after the loop's first barrier
@@ -3502,7 +3687,7 @@ SO_DEV void p_run_body(const PRunArgs& a, int nframes, const uint8_t* __restrict
 #ifdef SO_RUN_PROFILE
             const unsigned long long pt0 = __builtin_amdgcn_s_memtime();
 #endif
-            ptile_body<G, true, decltype(wait_ref), false, false, VBS, decltype(take_next), false, ZSKIP && !VBS, LISTS>(
+            ptile_body<G, true, decltype(wait_ref), false, false, VBS, decltype(take_next), false, ZSKIP && !VBS, LISTS, kFastTq>(
                 S, tile, a.cur[f], ref, H, W, 0, by1, qp_rd, qp_row, nullptr, nullptr, a.out[f], wait_ref, PHalo{}, lam,
                 &s_dense, reinterpret_cast<int32_t*>(tilefb) + (size_t)f * ntiles + tile, count_ops, take_next,
                 // VBS: the same hint for the block's U measured slower (4K VBS P-frame 123.1 vs
@@ -3545,6 +3730,15 @@ SO_DEV void p_run_body(const PRunArgs& a, int nframes, const uint8_t* __restrict
         if (fbsum != 0u)
             __hip_atomic_fetch_add(&ws[kRunFallbackWord], lane == 0 ? fbsum : 0u, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
+        if constexpr (kFastTq) {
+#pragma unroll
+            for (int d = 0; d < 2; ++d) {
+                const uint32_t n = __builtin_amdgcn_readfirstlane((uint32_t)S.msum[d]);
+                if (n != 0u)
+                    __hip_atomic_fetch_add(&ws[kRunTqFallbackWord + d], lane == 0 ? n : 0u, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
         const unsigned long long ops = s_ops;
         if (ops != 0ull)
             __hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(ws + kRunSadOpsWord), lane == 0 ? ops : 0ull,

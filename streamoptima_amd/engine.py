@@ -478,6 +478,18 @@ class Engine:
         ws[RUN_FALLBACK_WORD].zero_()
         return n
 
+    def take_tq_fallback_counts(self) -> tuple:
+        """(forward, inverse): wavefronts of the plain persistent runs since the last call whose
+        fast transform re-ran the pocketfft sequence (SO_P_RUN_TQ_FALLBACK_WORD); clears the
+        counts.  Synchronises."""
+        ws = getattr(self, "_run_ws", None)
+        if ws is None:
+            return 0, 0
+        w = ws[runhealth.TQ_FALLBACK_WORD:runhealth.TQ_FALLBACK_WORD + 2]
+        n = tuple(int(v) & 0xFFFFFFFF for v in w.cpu().tolist())
+        w.zero_()
+        return n
+
     def encode_i_rows(self, cur, by0: int, by1: int, qp_rd: int, out: FrameSymbols,
                       qp_row_dev: torch.Tensor | None = None, qp_map_dev: torch.Tensor | None = None,
                       qp_row=None) -> FrameSymbols:

@@ -17,6 +17,7 @@ GAP_WORD = 34
 CLAIM_WORD = 35
 FALLBACK_WORD = 64
 SAD_OPS_WORD = 66       # uint64 (words 66, 67)
+TQ_FALLBACK_WORD = 68   # words 68, 69: forward / inverse transform fallbacks (waves)
 DIAG_WORD = 96
 DIAG_MAGIC = 0x534F0001
 TICK_US = 0.01          # s_memrealtime: 100 MHz
