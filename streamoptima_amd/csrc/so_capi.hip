@@ -28,10 +28,7 @@ void set_error(const char* fmt, ...) {
 
 // so_set_option / so_get_option (SO_OPT_*): index = option id
 // SO_OPT_RUN_2PASS_FUSED on by default, SO_OPT_RUN_TALL_TILES unset (-1: chosen per launch)
-#ifndef SO_RUN_TALL_DEFAULT   // A/B builds: 0 = the 32-row twin unless the option is set
-#define SO_RUN_TALL_DEFAULT -1
-#endif
-static std::atomic<int> g_opt[9] = {0, 1, 0, 32, 32, 0, 0, 0, SO_RUN_TALL_DEFAULT};
+static std::atomic<int> g_opt[9] = {0, 1, 0, 32, 32, 0, 0, 0, -1};
 
 int option(int id) {
     return (id > 0 && id < 9) ? g_opt[id].load(std::memory_order_relaxed) : 0;

@@ -400,6 +400,9 @@ intra_recon_kernel(int H, int W, int by0, const uint8_t* __restrict__ split, con
 // the values already produced (sr <= 64, so x - src <= 64 + BS - 1 < 128 never aliases the
 // block being written).  nbx dependent steps of one LDS round trip each, instead of the
 // pointer-jumping kernel's log2(nbx) passes over the whole row with a barrier each.
+// blocks whose inputs are loaded one group ahead: the load latency is hidden behind 32 chain
+// steps (4K I-frame 102 -> 95 us vs 8, tools/intra_ab.py)
+constexpr int kIrsCh = 32;
 template <int BS, bool NEAR>
 __global__ void __launch_bounds__(256)
 intra_recon_seq_kernel(int W, int nrows_px, int by0, const uint8_t* __restrict__ split, const int16_t* __restrict__ mv,
@@ -420,10 +423,7 @@ intra_recon_seq_kernel(int W, int nrows_px, int by0, const uint8_t* __restrict__
     uint8_t* orow = out_recon + (size_t)yy * W;
     // the residuals and motion vectors of the next CH blocks are loaded while the current
     // CH blocks walk the chain (their loads do not depend on it)
-#ifndef SO_IRS_CH   // blocks whose inputs are loaded one group ahead: the load latency is
-#define SO_IRS_CH 32   // hidden behind 32 chain steps (4K I-frame 102 -> 95 us vs 8, tools/intra_ab.py)
-#endif
-    constexpr int CH = SO_IRS_CH;
+    constexpr int CH = kIrsCh;
     int resn[CH], dxn[CH], curn[CH];
     auto fetch = [&](int bx0, int (&rs)[CH], int (&dv)[CH], int (&cv)[CH]) {
 #pragma unroll
@@ -663,20 +663,20 @@ intra_recon_scan_kernel(int W, int nrows_px, int by0, const uint8_t* __restrict_
     }
 }
 
+constexpr int kIrsWpr = 4;   // waves per pixel row of the scan
+// waves per workgroup of the sequential kernel (a latency chain per wave; 1 spreads the 4K
+// I-frame's 540 waves over all 256 CUs instead of 135)
+constexpr int kIrsWpb = 1;
 // rows [0, nrows_px) of the stripe starting at block row by0: sequential kernel for sr <= 64
 static int intra_recon_rows(int W, int bs, int sr, int by0, int nrows_px, const uint8_t* split, const int16_t* mv,
                             const uint8_t* idres, const uint8_t* cur, uint8_t* out_recon, int32_t* out_sse, int H,
                             hipStream_t st) {
     if (nrows_px <= 0) return SO_OK;
-#ifndef SO_IRS_SEQ   // A/B builds: the sequential walk for sr <= bs too
     // 16-byte row loads / stores of cur and out_recon: W % 16 == 0 and 16-byte aligned planes
     // (the C-ABI takes any plane pointer; a misaligned one takes the sequential walk)
     const bool a16 = ((reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(out_recon)) & 15) == 0;
     if (sr <= bs && W % 16 == 0 && a16) {
-#ifndef SO_IRS_WPR   // waves per pixel row of the scan
-#define SO_IRS_WPR 4
-#endif
-        constexpr int WPR = SO_IRS_WPR, NT = 64 * WPR;
+        constexpr int WPR = kIrsWpr, NT = 64 * WPR;
         const int k = NT / bs, nbx = W / bs, L = (nbx + k - 1) / k;
         const size_t lds = (size_t)L * NT * sizeof(uint16_t) + NT * sizeof(uint32_t) + (size_t)W;
         const int nbr = (nrows_px + bs - 1) / bs, grid = (nbr + 7) / 8 * 8 * bs;   // whole groups of 8 block rows
@@ -688,17 +688,11 @@ static int intra_recon_rows(int W, int bs, int sr, int by0, int nrows_px, const 
                                split, mv, idres, cur, out_recon, out_sse);
         return check_launch("intra_recon_scan_kernel");
     }
-#endif
     if (sr <= 64) {
-        // SO_IRS_WPB waves per workgroup (the kernel is a latency chain per wave; 1 spreads
-        // the 4K I-frame's 540 waves over all 256 CUs instead of 135)
-#ifndef SO_IRS_WPB
-#define SO_IRS_WPB 1
-#endif
-        const int rows_per_blk = SO_IRS_WPB * (64 / bs);
+        const int rows_per_blk = kIrsWpb * (64 / bs);
         const dim3 grid((nrows_px + rows_per_blk - 1) / rows_per_blk);
 #define SO_IRS(B, N)                                                                                              \
-    hipLaunchKernelGGL((intra_recon_seq_kernel<B, N>), grid, dim3(64 * SO_IRS_WPB), 0, st, W, nrows_px, by0, split, \
+    hipLaunchKernelGGL((intra_recon_seq_kernel<B, N>), grid, dim3(64 * kIrsWpb), 0, st, W, nrows_px, by0, split, \
                        mv, idres, cur, out_recon, out_sse)
         if (bs == 16) { if (sr <= 16) SO_IRS(16, true); else SO_IRS(16, false); }
         else { if (sr <= 8) SO_IRS(8, true); else SO_IRS(8, false); }

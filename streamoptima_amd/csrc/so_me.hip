@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <array>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -617,35 +618,27 @@ int me_fme_launch(const uint8_t* cur, const uint8_t* planes, size_t pstride, int
 // 66-73 us per 4K P-frame, 23 us of it staging and 17 us compacting; it was retired once
 // this one replaced it.
 // ---------------------------------------------------------------------------------------
-#ifndef SO_SEA2_WPE
-#define SO_SEA2_WPE 6
-#endif
-#ifndef SO_SEA_CAP   // survivors per block evaluated from the list; more take the dense fallback
-#define SO_SEA_CAP 384   // round 6, 192 -> 384 (the list shares LDS with the transform scratch: no
-                         // cost in LDS): configs[4] 2.457 -> 2.41, low texture 2.186 -> 2.112, 4K
-                         // 1.568 -> 1.562 ms per GOP, noise unchanged; 512 and 768 slower
-                         // (profiles/r06/ab_sea_cap*.log)
-#endif
-#ifndef SO_SEA_CAP_VBS   // the same for a VBS block's block / sub-block lists (sea_vbs_block): looser
-#define SO_SEA_CAP_VBS 384   // sub-block bounds leave more survivors (4K VBS P-run 161.5 -> 158.8 us,
-                             // dense blocks 8.9 -> 3.8 %; 768: 161.5, profiles/r03/r03n/vbs_ab.log)
-#endif
-#ifndef SO_DENSE_THR     // a tile searches dense from the start when the same tile of the
-#define SO_DENSE_THR 8   // reference frame had at least this many of its 16 blocks overflow (a
-#endif                   // 24-block tile: 12, the same half), except every SO_DENSE_PROBE-th frame,
-                         // which probes the bound again
-#ifndef SO_DENSE_PROBE    // round 6, 4 -> 16: a probe frame pays the bound and the lists of every
-#define SO_DENSE_PROBE 16 // block before their dense search -- noise 3.13 -> 2.94 ms per 4K GOP (8:
-#endif                    // 3.01, 32: 2.91), textured content unchanged (ab_dense_probe_period.log)
-#ifndef SO_VBS_HALVES   // A/B builds: 1 = list B by halves.  Bit-exact, but 4K VBS GOP 3.198 ->
-#define SO_VBS_HALVES 0  // 3.359 ms (the second mask, list and four more wave minima cost more than
-#endif                   // the passes saved), 1080p 1.437 -> 1.375 (profiles/r06/ab_vbs_halves.log)
-#ifndef SO_B4_PD   // byte-sum rows in flight in the SEA bound loop (A/B builds: 3, 4)
-#define SO_B4_PD 2
-#endif
-#ifndef SO_PTILE_WPE16   // waves per SIMD of the 16-wave fused tile kernels (A/B builds only)
-#define SO_PTILE_WPE16 8
-#endif
+constexpr int kSea2Wpe = 6;   // waves per SIMD of the 8-wave search / fused tile / run kernels
+// survivors per block evaluated from the list; more take the dense fallback.  Round 6, 192 -> 384
+// (the list shares LDS with the transform scratch: no cost in LDS): configs[4] 2.457 -> 2.41, low
+// texture 2.186 -> 2.112, 4K 1.568 -> 1.562 ms per GOP, noise unchanged; 512 and 768 slower
+// (profiles/r06/ab_sea_cap*.log)
+constexpr int kSeaCap = 384;
+// the same for a VBS block's block / sub-block lists (sea_vbs_block): looser sub-block bounds
+// leave more survivors (4K VBS P-run 161.5 -> 158.8 us, dense blocks 8.9 -> 3.8 %; 768: 161.5,
+// profiles/r03/r03n/vbs_ab.log)
+constexpr int kSeaCapVbs = 384;
+// a tile searches dense from the start when the same tile of the reference frame had at least
+// this many of its 16 blocks overflow (a 24-block tile: 12, the same half), except every
+// kDenseProbe-th frame, which probes the bound again
+constexpr int kDenseThr = 8;
+// round 6, 4 -> 16: a probe frame pays the bound and the lists of every block before their dense
+// search -- noise 3.13 -> 2.94 ms per 4K GOP (8: 3.01, 32: 2.91), textured content unchanged
+// (ab_dense_probe_period.log)
+constexpr int kDenseProbe = 16;
+static_assert(kDenseProbe > 0 && (kDenseProbe & (kDenseProbe - 1)) == 0, "the probe period is applied as a bit mask");
+constexpr int kB4Pd = 2;   // byte-sum rows in flight in the SEA bound loop (3, 4: ab_tune_b4pd_cap320_448.log)
+constexpr int kPtileWpe16 = 8;   // waves per SIMD of the 16-wave fused tile kernels
 // NW_ waves per workgroup: 8 (two blocks per wave; me_sea2_kernel) or 16 (one block per
 // wave; p_tile_kernel at 8 waves/SIMD)
 // TPX_: tile width, 128 (8 blocks per block row)
@@ -672,12 +665,10 @@ struct Sea2GeoT {
     static constexpr int B4RS = B4NB * B4BAND;            // stored rows: whole bands, no bounds tests
     static constexpr int NBLK = TBX * TBY;
     static constexpr int NW = NW_, NTHREADS = NW * 64;
-    static constexpr int CAP = SO_SEA_CAP, CAPV = SO_SEA_CAP_VBS;
-    // list entries per wave (SO_VBS_HALVES: a VBS block's sub-block survivors go to two lists of
-    // up to CAPV, its top and bottom halves; in the fused tiles the lists share LDS with the
-    // transform scratch, which is larger either way)
-    static constexpr int CAPLV = SO_VBS_HALVES ? 2 * CAPV : CAPV;
-    static constexpr int CAPL = CAP > CAPLV ? CAP : CAPLV;
+    static constexpr int CAP = kSeaCap, CAPV = kSeaCapVbs;
+    // list entries per wave (in the fused tiles the lists share LDS with the transform scratch,
+    // which is larger)
+    static constexpr int CAPL = CAP > CAPV ? CAP : CAPV;
     static constexpr int DCS = WR * RP + 8;                // dense tiles: window copy stride (8 mod 32)
     static constexpr int CPD = TPX / 4 + 1;               // current-tile pitch in dwords: 16 rows of
                                                           // one block column land on 16 banks
@@ -791,16 +782,11 @@ struct NoPre {
 // Waves per SIMD the VBS run kernel is compiled for: 6 (three 8-wave workgroups per CU: 80
 // VGPRs, 53.2 KB of LDS) -- 4K VBS P-frame 120.4 vs 136.3 us at 4 waves / SIMD (128 VGPRs),
 // VALU busy 0.868 vs 0.735, 1.03x the VALU instructions (profiles/r05/vbs_ab4.log, pmc_vbs4)
-#ifndef SO_VBS_WPE
-#define SO_VBS_WPE 6
-#endif
-// SO_VBS_LEAN: the VBS search / transforms hold fewer values in VGPRs (block bounds recomputed
+constexpr int kVbsWpe = 6;
+// At 80 VGPRs the VBS search / transforms hold few values in registers (block bounds recomputed
 // where used, current rows re-read per survivor pass, levels requantised from the coefficients)
-// at the price of ~3 % more VALU -- what the 80-VGPR (6 waves / SIMD) build needs; at 128 VGPRs
-// (4 waves / SIMD) the plain forms are faster
-#ifndef SO_VBS_LEAN
-#define SO_VBS_LEAN (SO_VBS_WPE >= 6)
-#endif
+// at the price of ~3 % more VALU; the register-holding forms, faster only at 128 VGPRs (4 waves /
+// SIMD), were removed.
 // ---- VBSEnable: exact SEA for a block and its four 8x8 sub-blocks (sea_vbs_block) ----------
 // The block search of find_best_match plus the sub-block searches of inter_prediction
 // (Encoder.py:512-544: find_best_match of each 8x8 sub-block over its own +-16 window), for a
@@ -825,15 +811,8 @@ SO_DEV void vbs_eval_list(const Sea2Lds& L, const uint16_t* list, uint32_t n, in
     constexpr int RP = G::RP, CPD = G::CPD;
     const int sidx = lane >> 2, q = lane & 3;
     const int crow0 = byl * 16 * CPD + bxl * 4;
-    // SO_VBS_LEAN: the current rows are re-read from LDS per pass (a list is mostly one pass of
-    // 16): held across the loop they take 16 VGPRs while the 34 packed sub-bounds are live
-    uint32_t cr[4][4];
-    if constexpr (!SO_VBS_LEAN) {
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) cr[rr][k] = L.curt[crow0 + (4 * q + rr) * CPD + k];
-    }
+    // the current rows are re-read from LDS per pass (a list is mostly one pass of 16): held
+    // across the loop they take 16 VGPRs while the 34 packed sub-bounds are live
 #pragma unroll 1
     for (uint32_t s0 = 0; s0 < n; s0 += 16) {
         SO_MARK(vbs_pass);
@@ -850,8 +829,7 @@ SO_DEV void vbs_eval_list(const Sea2Lds& L, const uint16_t* list, uint32_t n, in
             lds_vu32p p = (lds_vu32p)(L.win + wo + rr * RP);
             lds_vu32p c = (lds_vu32p)(L.curt + crow0 + (4 * q + rr) * CPD);
             const uint32_t q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3], q4 = p[4];
-            const uint32_t c0 = SO_VBS_LEAN ? c[0] : cr[rr][0], c1 = SO_VBS_LEAN ? c[1] : cr[rr][1];
-            const uint32_t c2 = SO_VBS_LEAN ? c[2] : cr[rr][2], c3 = SO_VBS_LEAN ? c[3] : cr[rr][3];
+            const uint32_t c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
             sl = __builtin_amdgcn_sad_u8(c0, __builtin_amdgcn_alignbyte(q1, q0, sh), sl);
             sl = __builtin_amdgcn_sad_u8(c1, __builtin_amdgcn_alignbyte(q2, q1, sh), sl);
             srr = __builtin_amdgcn_sad_u8(c2, __builtin_amdgcn_alignbyte(q3, q2, sh), srr);
@@ -875,62 +853,15 @@ SO_DEV void vbs_eval_list(const Sea2Lds& L, const uint16_t* list, uint32_t n, in
     }
 }
 
-// List B by halves (SO_VBS_HALVES): a candidate not in list A can only improve sub-block
-// minima, and mostly passes one sub-block bound, so B holds (candidate, half) entries -- the
-// top half's list at listT, the bottom half's at listBo -- and a pass evaluates 16 entries of
-// each: lanes 0-31 the top ones, lanes 32-63 the bottom ones, two lanes per entry (4 of its
-// 8 rows each), paired by one DPP add into the half's left / right quadrant SADs.  32-bit
-// sub-block keys as vbs_eval_list's, into c0 (left quadrant) and c1 (right) of the lane's half.
-template <class G>
-SO_DEV void vbs_eval_halves(const Sea2Lds& L, const uint16_t* listT, uint32_t nT, const uint16_t* listBo,
-                            uint32_t nBo, int cs, int bxl, int byl, int lane, uint32_t& c0, uint32_t& c1) {
-    constexpr int RP = G::RP, CPD = G::CPD;
-    const bool bot = lane >= 32;
-    const int e = (lane & 31) >> 1;
-    const int r0 = (bot ? 8 : 0) + 4 * (lane & 1);
-    const uint16_t* const list = bot ? listBo : listT;
-    const uint32_t n = bot ? nBo : nT, nmax = nT > nBo ? nT : nBo;
-    const int crow0 = byl * 16 * CPD + bxl * 4 + r0 * CPD;
-#pragma unroll 1
-    for (uint32_t s0 = 0; s0 < nmax; s0 += 16) {
-        SO_MARK(vbs_pass);
-        const bool act = s0 + (uint32_t)e < n;
-        const int cand = act ? (int)list[s0 + e] : cs;
-        const int dxi = cand / 33, di = cand - dxi * 33;
-        const int col = bxl * 16 + dxi;
-        const uint32_t sh = (uint32_t)(col & 3);
-        int wo = (byl * 16 + di + r0) * RP + (col >> 2);
-        asm volatile("" : "+v"(wo));
-        uint32_t sl = 0, srr = 0;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            lds_vu32p p = (lds_vu32p)(L.win + wo + rr * RP);
-            lds_vu32p c = (lds_vu32p)(L.curt + crow0 + rr * CPD);
-            const uint32_t q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3], q4 = p[4];
-            sl = __builtin_amdgcn_sad_u8(c[0], __builtin_amdgcn_alignbyte(q1, q0, sh), sl);
-            sl = __builtin_amdgcn_sad_u8(c[1], __builtin_amdgcn_alignbyte(q2, q1, sh), sl);
-            srr = __builtin_amdgcn_sad_u8(c[2], __builtin_amdgcn_alignbyte(q3, q2, sh), srr);
-            srr = __builtin_amdgcn_sad_u8(c[3], __builtin_amdgcn_alignbyte(q4, q3, sh), srr);
-        }
-        uint32_t v = sl | (srr << 16);
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kDppQuad1032, 0xF, 0xF, false);   // lanes l, l ^ 1
-        const int dx = dxi - 16, dy = di - 16;
-        const uint32_t md = (uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy));
-        const uint32_t t32 = (md << 11) | (uint32_t)cand;
-        const uint32_t k0 = ((v & 0xFFFFu) << 17) | t32, k1 = ((v >> 16) << 17) | t32;
-        c0 = (act && k0 < c0) ? k0 : c0;
-        c1 = (act && k1 < c1) ? k1 : c1;
-    }
-}
-
-#ifndef SO_VBS_BALLOT_LATENCY   // A/B builds: 0 = mask-built lists in latency-bound runs too.
-#define SO_VBS_BALLOT_LATENCY 1  // 1080p VBS GOP 1.433 -> 1.399 ms (profiles/r06/ab_vbs_ballot_
-#endif                           // latency.log); the uniform-QP run as two instantiations, 4K
-                                 // unchanged (ab_vbs_latency_twin.log)
-#ifndef SO_VBS_MASKLIST   // bit 0: list A, bit 1: list B built from masks (0: one ballot per
-#define SO_VBS_MASKLIST 3   // candidate row, round 5).  4K VBS GOP 3.271 -> 3.201 ms (B alone 3.212,
-#endif                      // A alone 3.251); 1080p VBS 1.394 -> 1.430, latency-bound there (a wave
-                            // runs its lanes' longest bit loop) -- profiles/r06/ab_vbs_masklist*.log
+// Both lists are built from masks where the run is throughput-bound: 4K VBS GOP 3.271 -> 3.201 ms
+// (B alone 3.212, A alone 3.251) against one ballot per candidate row; 1080p VBS 1.394 -> 1.430,
+// latency-bound there (a wave runs its lanes' longest bit loop) -- profiles/r06/ab_vbs_masklist*.log.
+// So a latency-bound run keeps the ballot build (`ballot_lists`): 1080p VBS GOP 1.433 -> 1.399 ms
+// (profiles/r06/ab_vbs_ballot_latency.log); the uniform-QP run as two instantiations, 4K
+// unchanged (ab_vbs_latency_twin.log).
+// List B by (candidate, half) entries -- 32 halves per pass -- was bit-exact but slower, 4K VBS
+// GOP 3.198 -> 3.359 ms (the second mask, list and four more wave minima cost more than the
+// passes saved), 1080p 1.437 -> 1.375 (profiles/r06/ab_vbs_halves.log): removed.
 // A VBS survivor list from per-lane candidate masks (bit t < NT: candidate cbase + t; bit NT:
 // c2, the dx = +16 column's): each lane's entries at its offset in the wave's prefix sum of the
 // masks' popcounts, the set bits written in a loop the wave runs max-popcount times (the lists'
@@ -1015,16 +946,10 @@ SO_DEV bool sea_vbs_block(const Sea2Lds& L, int u, int bxl, int byl, int tid, bo
             acc = __builtin_amdgcn_sad_hi_u8(AR[j], qv & 0xFFFF0000u, __builtin_amdgcn_sad_u8(AL[j], qv & 0xFFFFu, acc));
         }
     }
-    // block bounds LBq(t): the four sub-block bounds summed (SO_VBS_LEAN: recomputed where used,
-    // the list-A test, instead of held in 17 more VGPRs through the lists)
+    // block bounds LBq(t): the four sub-block bounds summed (recomputed where used, the list-A
+    // test, instead of held in 17 more VGPRs through the lists)
     SO_MARK(vbs_umin);
-    const auto blb0 = [&](int t) { return __builtin_amdgcn_sad_u16(T[t], 0u, __builtin_amdgcn_sad_u16(Bt[t], 0u, 0u)); };
-    uint32_t lbs[SO_VBS_LEAN ? 1 : NT];
-    if constexpr (!SO_VBS_LEAN) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) lbs[t] = blb0(t);
-    }
-    const auto blb = [&](int t) { return SO_VBS_LEAN ? blb0(t) : lbs[SO_VBS_LEAN ? 0 : t]; };
+    const auto blb = [&](int t) { return __builtin_amdgcn_sad_u16(T[t], 0u, __builtin_amdgcn_sad_u16(Bt[t], 0u, 0u)); };
     const uint32_t lb2 = __builtin_amdgcn_sad_u16(l2T, 0u, __builtin_amdgcn_sad_u16(l2B, 0u, 0u));
     const bool ok2 = lane < 33;
     // ---- 2. U and the block survivors (A) -------------------------------------------------------
@@ -1059,7 +984,7 @@ SO_DEV bool sea_vbs_block(const Sea2Lds& L, int u, int bxl, int byl, int tid, bo
     uint16_t* const mylist = L.list + wave * G::CAPL;
     const int cbase = xi * 33 + 16 * hh;
     uint32_t nA = 0;
-    if ((SO_VBS_MASKLIST & 1) != 0 && !ballot_lists) {
+    if (!ballot_lists) {
         nA = vbs_list_from_masks<NT>(mylist, amask | ((ok2 && lb2 <= qU) ? 1u << NT : 0u), cbase, 32 * 33 + d2,
                                      (uint32_t)CAP);
     } else {
@@ -1100,54 +1025,8 @@ SO_DEV bool sea_vbs_block(const Sea2Lds& L, int u, int bxl, int byl, int tid, bo
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // list A read before it is overwritten
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if constexpr (SO_VBS_HALVES) {
-        // (candidate, half) entries: the top list at mylist, the bottom one at mylist + CAP
-        const auto pass_half = [](uint32_t v, uint32_t th) {
-            const so_v2i16 d = __builtin_bit_cast(so_v2i16, v) - __builtin_bit_cast(so_v2i16, th);
-            return (__builtin_bit_cast(uint32_t, d) & 0x80008000u) != 0u;
-        };
-        uint32_t mT = 0, mBo = 0;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            mT |= (pass_half(T[t], thT) ? 1u : 0u) << t;
-            mBo |= (pass_half(Bt[t], thB) ? 1u : 0u) << t;
-        }
-        const bool col_b = ok2 && !(lb2 <= qU);
-        mT = (mT & ~amask) | ((col_b && pass_half(l2T, thT)) ? 1u << NT : 0u);
-        mBo = (mBo & ~amask) | ((col_b && pass_half(l2B, thB)) ? 1u << NT : 0u);
-        const uint32_t nT = vbs_list_from_masks<NT>(mylist, mT, cbase, 32 * 33 + d2, (uint32_t)CAP);
-        const uint32_t nBo = vbs_list_from_masks<NT>(mylist + CAP, mBo, cbase, 32 * 33 + d2, (uint32_t)CAP);
-        if (nT > (uint32_t)CAP || nBo > (uint32_t)CAP) return false;
-        const uint32_t nmax = nT > nBo ? nT : nBo;
-        if (lane == 0) SO_OPS_ADD(&L.st[2], 16u * ((nmax + 15) / 16) * 256u);   // 32 half-candidates per pass
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint64_t kb = wave_min_u64_dpp(bestB);
-        uint32_t c0 = ~0u, c1 = ~0u;
-        vbs_eval_halves<G>(L, mylist, nT, mylist + CAP, nBo, cs, bxl, byl, lane, c0, c1);
-        SO_MARK(vbs_final);
-        const auto widen = [](uint32_t k) {
-            return ((uint64_t)(k >> 17) << 32) | ((uint64_t)((k >> 11) & 63u) << 24) | (uint64_t)(k & 2047u);
-        };
-        const bool bot = lane >= 32;
-        const uint32_t hTL = wave_min_u32(bot ? ~0u : c0), hTR = wave_min_u32(bot ? ~0u : c1);
-        const uint32_t hBL = wave_min_u32(bot ? c0 : ~0u), hBR = wave_min_u32(bot ? c1 : ~0u);
-        const uint64_t kTL = widen(hTL < mTL ? hTL : mTL), kTR = widen(hTR < mTR ? hTR : mTR);
-        const uint64_t kBL = widen(hBL < mBL ? hBL : mBL), kBR = widen(hBR < mBR ? hBR : mBR);
-        if (lane == 0) {
-            unsigned long long* const ks = L.keys;
-            if (kb < ks[u]) ks[u] = kb;
-            unsigned long long* const sk = ks + G::NBLK + 4 * u;
-            if (kTL < sk[0]) sk[0] = kTL;
-            if (kTR < sk[1]) sk[1] = kTR;
-            if (kBL < sk[2]) sk[2] = kBL;
-            if (kBR < sk[3]) sk[3] = kBR;
-        }
-        return true;
-    }
     uint32_t nB = 0;
-    if ((SO_VBS_MASKLIST & 2) != 0 && !ballot_lists) {
+    if (!ballot_lists) {
         uint32_t mB = 0;
 #pragma unroll
         for (int t = 0; t < NT; ++t) mB |= (any_sub(T[t], Bt[t]) ? 1u : 0u) << t;
@@ -1214,9 +1093,6 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
                       const int* dense_flag = nullptr, const int16_t* prev_mv = nullptr) {
     constexpr int SR = G::SR, TBX = G::TBX, TBY = G::TBY, RP = G::RP, NT = G::NT;
     constexpr int B4P = G::B4P, CAP = G::CAP, CP = G::TPX;
-#ifdef SO_NO_MV_HINT   // A/B builds: U from the smallest-bound candidate only
-    prev_mv = nullptr;
-#endif
     uint32_t* const win = L.win;
     uint32_t* const b4w = L.b4w;
     uint8_t* const b4 = reinterpret_cast<uint8_t*>(b4w);
@@ -1230,8 +1106,8 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
     const int tx = tile % tiles_x, ty = tile / tiles_x;
     // a persistent grid with more slots than a frame has tiles runs latency-bound (the chain
     // step of one tile position): there the VBS lists are built one ballot per candidate row,
-    // whose cost does not depend on how the survivors cluster in a lane (SO_VBS_MASKLIST)
-    const bool ballot_lists = LISTS == 2 || (LISTS == 0 && SO_VBS_BALLOT_LATENCY && VBS &&
+    // whose cost does not depend on how the survivors cluster in a lane (vbs_list_from_masks)
+    const bool ballot_lists = LISTS == 2 || (LISTS == 0 && VBS &&
                                              tiles_x * ((H / 16 + TBY - 1) / TBY) < (int)gridDim.x);
     const int bx0 = tx * TBX, byt0 = by0 + ty * TBY;
     const int x0 = bx0 * 16, y0 = byt0 * 16;
@@ -1318,17 +1194,11 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
     // Blocks of the tile go to waves dynamically: wave w starts with block w, then takes the
     // next unclaimed one (an LDS counter), so a wave stuck on a many-survivor or dense-fallback
     // block no longer holds a second block back while the others wait at the barrier.
-    // (SO_SEA_STATIC: the fixed u = w, w + NW assignment, A/B builds only.)
     uint32_t* const grab = L.lcount;
-    const auto next_block = [&](int u) -> int {
-#ifdef SO_SEA_STATIC
-        return u + G::NW;
-#else
-        (void)u;
+    const auto next_block = [&](int) -> int {
         uint32_t nx = 0;
         if ((tid & 63) == 0) nx = __hip_atomic_fetch_add(grab, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         return (int)__builtin_amdgcn_readfirstlane(nx);
-#endif
     };
     for (int r = 0; r < nref; ++r) {
         const uint8_t* ref = refs.p[r];
@@ -1466,18 +1336,14 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
                     *reinterpret_cast<const uint32_t*>(prev_mv + ((size_t)(byt0 + byl - by0) * nbx + bx0 + bxl) * 12));
             if constexpr (VBS) {
                 if (x != 0 && y != 0) {   // uniform: block + sub-block search
-#ifndef SO_VBS_DENSE_ONLY   // A/B builds: every sub-searched block dense
                     if (x + 48 <= W && y + 48 <= H && sea_vbs_block<G>(L, u, bxl, byl, tid, ballot_lists)) continue;
-#endif
                     if ((tid & 63) == 0) {
                         atomicAdd(&st_fb, 1u);   // counted as a dense fallback
                         SO_OPS_ADD(&st_ops, kDenseSadOps);
                     }
-#ifndef SO_TEST_NODENSE
                     SO_MARK(vbs_dense);
                     wave_dense_block<16, true, RP, 0, false, true>(win, keys, G::NBLK, cur, W, H, x, y, bxl, byl, u,
                                                                    tid, r);
-#endif
                     continue;
                 }
             }
@@ -1495,12 +1361,7 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             const uint32_t bsh = (uint32_t)lb0 & 3;
             int lo1 = lb0 >> 2;
             asm volatile("" : "+v"(lo1));
-#ifdef SO_B4_READ2   // A/B: plain (mergeable into ds_read2_b32) reads of the byte-sum rows
-            typedef const __attribute__((address_space(3))) uint32_t* lds_u32p_;
-            lds_u32p_ p1 = (lds_u32p_)(b4w + lo1);
-#else
             lds_vu32p p1 = (lds_vu32p)(b4w + lo1);
-#endif
             // lb[t] = (LBq << 16) | t: v_sad_hi_u8 accumulates each sum << 16 onto the initial t
             // (an inline constant), so the smallest-bound key below needs no shifts or ORs
             // (LBq <= 16 * 255 < 2^16)
@@ -1510,7 +1371,7 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             // byte-sum rows through a ring of PD rows in flight: the row used in step sr_ was
             // loaded PD steps earlier, so LDS latency overlaps PD steps of v_sad_u8 work
             // (one step ahead left every step waiting on its own loads)
-            constexpr int PD = SO_B4_PD;
+            constexpr int PD = kB4Pd;
             uint32_t n0[PD], n1[PD];
 #pragma unroll
             for (int k = 0; k < PD; ++k) { n0[k] = p1[k * (B4P / 4)]; n1[k] = p1[k * (B4P / 4) + 1]; }
@@ -1726,7 +1587,7 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
     __syncthreads();
 }
 
-__global__ void __launch_bounds__(Sea2Geo::NTHREADS) __attribute__((amdgpu_waves_per_eu(SO_SEA2_WPE)))
+__global__ void __launch_bounds__(Sea2Geo::NTHREADS) __attribute__((amdgpu_waves_per_eu(kSea2Wpe)))
 me_sea2_kernel(const uint8_t* __restrict__ cur, RefSet refs, int nref, int H, int W, int by0, int by1,
                int32_t* __restrict__ out_best, int probe) {
     using G = Sea2Geo;
@@ -1796,9 +1657,6 @@ me_sea2_kernel(const uint8_t* __restrict__ cur, RefSet refs, int nref, int H, in
 constexpr int kTqScratch = 16 * 17;
 // The tokens-only pass-1 tile (p_tile_kernel<8, true>) transforms through half of it (16 x 9,
 // xform2d_fwd_i_half): 33.7 KB of LDS per workgroup, four workgroups per CU instead of three
-#ifndef SO_PTILE_TOK_HALF
-#define SO_PTILE_TOK_HALF 1
-#endif
 constexpr int kTqScratchHalf = 16 * 9;
 // a geometry with TQDW: 16 x 17 dwords per block (xform2d_rows_dw, both transforms), in doubles
 constexpr int kTqScratchDw = 16 * 17 / 2;
@@ -1899,14 +1757,7 @@ struct PHalo {
 // `qs` (fwd_mfma): the block's levels, already certified (16 x 16 int16 at the start of
 // `scratch`); null = run the FP64 forward transform here.
 // The twiddles of tq16_exact's transforms: scalar loads from the constant table, behind one
-// optimisation barrier per 2-D transform (dct::tw16_table); -DSO_TQ_TW_LITERAL: as literals.
-#ifdef SO_TQ_TW_LITERAL
-#define SO_TQ_TW() dct::TW16{}
-#define SO_TQ_TW8() dct::TW8{}
-#else
-#define SO_TQ_TW() dct::tw16_table()
-#define SO_TQ_TW8() dct::tw8_table()
-#endif
+// optimisation barrier per 2-D transform (dct::tw16_table, dct::tw8_table).
 // ZSKIP (SO_OPT_RUN_ZERO_SKIP): a wave whose four blocks all quantised to zero skips the IDCT
 // FAST (SO_TQ_FAST, the plain one-GPU run): both 2-D transforms by the fast passes of so_dct.h
 // (xform2d_fast), each with a certificate and the pocketfft sequence as the wave's fallback:
@@ -2060,18 +1911,18 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
                     rows_of(g, l, prow2, pcol2, crow2);
                     load_res(prow2, pcol2, crow2);
                     if constexpr (G::TQDW)
-                        xform2d_rows_dw<false>(dl, l, res, tcr, SO_TQ_TW());
+                        xform2d_rows_dw<false>(dl, l, res, tcr, dct::tw16_table());
                     else
-                        xform2d_rows<16, false>(dl, l, res, tcr, SO_TQ_TW());
+                        xform2d_rows<16, false>(dl, l, res, tcr, dct::tw16_table());
                     quant_fma(false);
                 }
             } else {
             if constexpr (HALFTQ)
-                xform2d_fwd_i_half(dl, l, res, tcr, SO_TQ_TW());
+                xform2d_fwd_i_half(dl, l, res, tcr, dct::tw16_table());
             else if constexpr (G::TQDW)
-                xform2d_rows_dw<false>(dl, l, res, tcr, SO_TQ_TW());
+                xform2d_rows_dw<false>(dl, l, res, tcr, dct::tw16_table());
             else
-                xform2d_rows<16, false>(dl, l, res, tcr, SO_TQ_TW());
+                xform2d_rows<16, false>(dl, l, res, tcr, dct::tw16_table());
             SO_MARK(tq_quant);
 #pragma unroll
             for (int c = 0; c < 16; ++c)
@@ -2145,9 +1996,9 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
             dequant_row_int<16>(ql, l, qpr, dq);
             if constexpr (!FAST) SO_MARK(tq_inv);
             if constexpr (G::TQDW)
-                xform2d_rows_dw<true>(dl, l, dq, rd, SO_TQ_TW());
+                xform2d_rows_dw<true>(dl, l, dq, rd, dct::tw16_table());
             else
-                xform2d_rows<16, true>(dl, l, dq, rd, SO_TQ_TW());
+                xform2d_rows<16, true>(dl, l, dq, rd, dct::tw16_table());
             if constexpr (!FAST) SO_MARK(tq_recon);
             derive();
             int rec[16];
@@ -2474,7 +2325,7 @@ SO_DEV void tq16_vbs_fwd(PTileLds<G, true>& S, int g, int l, double* scratch, in
             for (int e = 0; e < 4; ++e) res[4 * k + e] = (int)((cw >> (8 * e)) & 255) - (int)((pw[k] >> (8 * e)) & 255);
         }
         double tcr[16];
-        xform2d_rows<16, false>(scratch, l, res, tcr, SO_TQ_TW());
+        xform2d_rows<16, false>(scratch, l, res, tcr, dct::tw16_table());
         int tc[16], q[16];
 #pragma unroll
         for (int c = 0; c < 16; ++c) tc[c] = (int)__builtin_rint(tcr[c]);
@@ -2508,7 +2359,7 @@ SO_DEV void tq16_vbs_fwd(PTileLds<G, true>& S, int g, int l, double* scratch, in
             }
         }
         double std_[2][8];
-        xform2d_sub<false>(scratch, l, sres, std_, SO_TQ_TW8());
+        xform2d_sub<false>(scratch, l, sres, std_, dct::tw8_table());
         int stc[2][8], qs[2][8];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -2649,7 +2500,7 @@ SO_DEV void tq16_vbs_inv(PTileLds<G, true>& S, int k, int l, double* un, int bx0
         load_row_i16<16>(o.qtc + b * 256 + l * 16, q);
         dequant_row_int<16>(q, l, qpr, dq);
         double rd[16];
-        xform2d_rows<16, true>(scratch, l, dq, rd, SO_TQ_TW());
+        xform2d_rows<16, true>(scratch, l, dq, rd, dct::tw16_table());
         int rec[16];
         {
             uint32_t pw[4];
@@ -2690,7 +2541,7 @@ SO_DEV void tq16_vbs_inv(PTileLds<G, true>& S, int k, int l, double* un, int bx0
             }
         }
         double srd[2][8];
-        xform2d_sub<true>(scratch, l, sdq, srd, SO_TQ_TW8());
+        xform2d_sub<true>(scratch, l, sdq, srd, dct::tw8_table());
         const int xs = x + (j & 1) * 8, ys = y + (j >> 1) * 8;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -2750,12 +2601,10 @@ SO_DEV void ptile_body(PTileLds<G, VBS, HALFTQ>& S, int tile, const uint8_t* __r
     // room for a dense tile's three shifted window copies in the scratch, 8 (mod 32) dwords on
     constexpr int kUnDw = 2 * (VBS ? PTileGeoVbs<G>::U64 : PTileGeo<G, HALFTQ>::U64);
     int dense4 = 0;
-#ifndef SO_DENSE_ONE   // A/B builds: dense tiles read the single window copy
     if constexpr (3 * G::DCS + 32 <= kUnDw) {
         const int d = (int)((reinterpret_cast<uintptr_t>(b4w) - reinterpret_cast<uintptr_t>(S.win)) / 4);
         dense4 = d + ((8 - d) & 31);
     }
-#endif
     const Sea2Lds L{S.win, b4w, S.curt, S.a4, list, S.lcount, S.keys, S.st, count_ops, dense4};
     RefSet refs{};
     refs.p[0] = ref;
@@ -2897,7 +2746,7 @@ SO_DEV void tq16_pass1(PTileLds<G>& S, int g, int l, double* scratch, int bx0, i
             asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(rp), "v"(pv) : "memory");
         }
         double tcr[16];
-        xform2d_rows<16, false>(scratch, l, res, tcr, SO_TQ_TW());
+        xform2d_rows<16, false>(scratch, l, res, tcr, dct::tw16_table());
         // TC = np.round(DCT) as int32 (the 1.5 * 2^52 shift rounds half to even, as rint), the
         // pass-1 levels at the row QP by the exact integer round-half-even shift
         constexpr double kRne = 0x1.8p52;
@@ -2966,7 +2815,7 @@ SO_DEV void tq16_pass2(PTileLds<G>& S, int g, int l, double* scratch, int bx0, i
         // No address here derives from another task's output: pass 1 left the prediction rows
         // in the block's reconstruction rows and the coefficients in its QTC rows.  (Round 5
         // read pass 1's motion vector and loaded the prediction at it: after a timed-out wait,
-        // when the run's later waits return at once (SO_RUN_ABORT_CHECK), a pass-2 unit could
+        // when the run's later waits return at once (run_poll, after a timeout), a pass-2 unit could
         // run before its row's pass 1 and address ~125 MB past the plane with an unwritten
         // record -- the frame pipeline's hipErrorIllegalAddress)
         int qpr;
@@ -2989,7 +2838,7 @@ SO_DEV void tq16_pass2(PTileLds<G>& S, int g, int l, double* scratch, int bx0, i
         int dq[16];
         double rd[16];
         dequant_row_int<16>(q, l, qpr, dq);
-        xform2d_rows<16, true>(scratch, l, dq, rd, SO_TQ_TW());
+        xform2d_rows<16, true>(scratch, l, dq, rd, dct::tw16_table());
         int rec[16];
         {
             uint32_t pw[4];
@@ -3031,17 +2880,15 @@ SO_DEV void tq16_pass2(PTileLds<G>& S, int g, int l, double* scratch, int bx0, i
     }
 }
 
-#ifndef SO_PTILE_NW
-#define SO_PTILE_NW 8
-#endif
+constexpr int kPtileNw = 8;   // waves per workgroup of the fused tile and run kernels
 template <int NW, bool TOK = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
-    NW >= 16 ? SO_PTILE_WPE16 : (TOK && SO_PTILE_TOK_HALF ? 8 : SO_SEA2_WPE))))
+    NW >= 16 ? kPtileWpe16 : (TOK ? 8 : kSea2Wpe))))
 p_tile_kernel(const uint8_t* __restrict__ cur, RefSet refs, int H, int W, int by0, int by1, int qp_rd,
               const int32_t* __restrict__ qp_row, const int32_t* __restrict__ qp_map, int32_t* __restrict__ out_best,
               PFrameOut o, const int16_t* prev_mv) {
     using G = Sea2GeoT<NW>;
-    __shared__ PTileLds<G, false, TOK && SO_PTILE_TOK_HALF> S;
+    __shared__ PTileLds<G, false, TOK> S;
     SO_STAMP_REC_SET(g_sea_stamps ? g_sea_stamps + (size_t)blockIdx.x * 12 : nullptr);
     ptile_body<G, false, NoPre, false, TOK>(S, blockIdx.x, cur, refs.p[0], H, W, by0, by1, qp_rd, qp_row, qp_map,
                                             out_best, o, NoPre(), PHalo{}, 0.0, nullptr, nullptr, 0, NoPre(), prev_mv);
@@ -3069,10 +2916,10 @@ int p_tile_launch(const uint8_t* cur, const RefSet& refs, int H, int W, int by0,
     const dim3 grid(((nbx + Sea2Geo::TBX - 1) / Sea2Geo::TBX) * ((nrows + Sea2Geo::TBY - 1) / Sea2Geo::TBY));
     const PFrameOut o{out_split, out_mv, out_qtc, out_tokens, out_mae, out_recon, out_sse, nullptr};
     if (tokens_only)
-        hipLaunchKernelGGL((p_tile_kernel<SO_PTILE_NW, true>), grid, dim3(SO_PTILE_NW * 64), 0, st, cur, refs, H, W,
+        hipLaunchKernelGGL((p_tile_kernel<kPtileNw, true>), grid, dim3(kPtileNw * 64), 0, st, cur, refs, H, W,
                            by0, by1, qp_rd, qp_row, qp_map, out_best, o, prev_mv);
     else
-        hipLaunchKernelGGL((p_tile_kernel<SO_PTILE_NW, false>), grid, dim3(SO_PTILE_NW * 64), 0, st, cur, refs, H, W,
+        hipLaunchKernelGGL((p_tile_kernel<kPtileNw, false>), grid, dim3(kPtileNw * 64), 0, st, cur, refs, H, W,
                            by0, by1, qp_rd, qp_row, qp_map, out_best, o, prev_mv);
     return check_launch("p_tile_kernel");
 }
@@ -3096,21 +2943,9 @@ struct PRunArgs {
 // workgroup resets [0], [1] and stores the epoch in [2], so no launch needs a memset.  [32] is
 // the CALLER's: it accumulates over launches and calls until the caller reads and clears it
 // (Engine.check_run), so a timeout in any launch of a GOP is seen.
-#ifndef SO_RUN_ACQUIRE
-#define SO_RUN_ACQUIRE 1
-#endif
-#ifndef SO_RUN_ABORT_CHECK
-#define SO_RUN_ABORT_CHECK 1
-#endif
-#ifndef SO_RUN_TIMEOUT_WORD
-#define SO_RUN_TIMEOUT_WORD 32
-#endif
-#ifndef SO_RUN_DONE_BASE
-#define SO_RUN_DONE_BASE 128
-#endif
 // the task counter (hammered by every workgroup's dequeue), the timeout count, the fallback and
 // SAD counts, the wait diagnostic record and the done flags live on separate 128-byte lines
-constexpr int kRunTimeoutWord = SO_RUN_TIMEOUT_WORD, kRunDoneBase = SO_RUN_DONE_BASE;
+constexpr int kRunTimeoutWord = 32, kRunDoneBase = 128;
 // [1], [2] on the task counter's line: touched once per workgroup.  [64] (a line of its own):
 // blocks whose SEA search took the dense fallback, summed over launches until the caller clears
 // it (SO_P_RUN_FALLBACK_WORD); each workgroup adds its total once, on its way out.  (Adding per
@@ -3132,10 +2967,7 @@ constexpr int kRunTqFallbackWord = SO_P_RUN_TQ_FALLBACK_WORD;
 constexpr int kRunStaleWord = SO_P_RUN_STALE_WORD, kRunGapWord = SO_P_RUN_GAP_WORD, kRunClaimWord = 35;
 constexpr int kRunDiagWord = SO_P_RUN_DIAG_WORD;
 static_assert(kRunDoneBase >= kRunDiagWord + 32, "the diagnostic record precedes the done flags");
-// kRunFPipe2P: the frame pipeline with two-pass RC (each tile a pass-1 and a pass-2 task as
-// kRunTwoPass; the reference arrives in the landing planes as kRunFPipe, and pass 2 pushes
-// the final reconstruction on to the rank encoding the next frame)
-constexpr int kRunSingle = 0, kRunStripe = 1, kRunFPipe = 2, kRunTwoPass = 3, kRunFPipe2P = 4;
+// (the run kinds kRunSingle .. kRunFPipe2P: so_run_select.h)
 // SO_RUN_PROFILE builds (tools/rc2p_ab.py): per-phase shader cycles >> 10 accumulated by wave 0
 // into workspace words 48.. (48 pass-1 task, 49 pass-2 task, 50 pass-2 row wait, 51 reference
 // wait); A/B diagnostics only
@@ -3187,7 +3019,6 @@ SO_DEV uint32_t run_poll(const uint32_t* c, bool need, bool sysl, uint32_t* ws, 
         const bool ok = raw == (sysl ? w.sys_want : w.want);
         SO_MARK(poll_iter);
         if (__builtin_amdgcn_ballot_w64(need && !ok) == 0) break;
-#if SO_RUN_ABORT_CHECK
         // the timeout count, read once per wait and only when it has to wait: after one timeout
         // the later waits of the run return at once (the run is already flagged wrong), so a
         // lost flag cannot stall the launch for 50 ms per remaining tile.  (Read ahead of every
@@ -3199,7 +3030,6 @@ SO_DEV uint32_t run_poll(const uint32_t* c, bool need, bool sysl, uint32_t* ws, 
                                                                  __HIP_MEMORY_SCOPE_AGENT)) != 0u)
                 break;
         }
-#endif
         __builtin_amdgcn_s_sleep(1);
         const uint32_t now = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t0), gap = now - last;
         last = now;
@@ -3312,13 +3142,10 @@ SO_DEV uint32_t run_dequeue(uint32_t* ws) {
 // kernels sharing this body: p_run_kernel on 128 x 48 tiles (24 blocks, the dword transform
 // scratch) and p_run_short_kernel on the 128 x 32 tiles of every other run; the host picks per
 // launch (p_run_tall_choice).
-#ifndef SO_RUN_SHORT_TQDW   // A/B builds: the short plain run's transforms through the dword scratch
-#define SO_RUN_SHORT_TQDW 0  // (xform2d_rows_dw alone, on 32-row tiles)
-#endif
 template <int NW>
 using RunGeoTall = Sea2GeoT<NW, 128, 3, true>;
 template <int NW>
-using RunGeoShort = Sea2GeoT<NW, 128, 2, SO_RUN_SHORT_TQDW != 0>;
+using RunGeoShort = Sea2GeoT<NW, 128, 2, false>;
 template <int MODE, bool VBS, bool HOOKS, bool UQP>
 constexpr bool kRunHasTall = MODE == kRunSingle && !VBS && !HOOKS && !UQP;
 template <class G, int MODE, bool VBS, bool HOOKS, bool UQP, bool ZSKIP>
@@ -3386,15 +3213,11 @@ SO_DEV void p_run_body(const PRunArgs& a, int nframes, const uint8_t* __restrict
     // flags hold the epoch of the launch that set them: nothing is zeroed between launches.
     const uint32_t ep0 = __builtin_amdgcn_readfirstlane(
         __hip_atomic_load(&ws[kRunEpochWord], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) + 1u;
-#ifndef SO_EP_REG
     // inside the loop the epoch is re-read from LDS where it is used: a register held across
     // the persistent loop was spilled to scratch and reloaded per task on wave 0's path
     __shared__ uint32_t s_ep;
     if (tid == 0) s_ep = ep0;   // visible after the dequeue barrier below
 #define ep ((uint32_t)__builtin_amdgcn_readfirstlane(*(lds_vu32p)&s_ep))
-#else
-    const uint32_t ep = ep0;
-#endif
     // The plain run dequeues its next task at the end of the current one (ptile_body's `post`,
     // before the drain of the tile's stores), so the atomic's round trip overlaps the drain
     // instead of following the done flag.  Still deadlock-free: a workgroup holds at most one
@@ -3503,32 +3326,26 @@ SO_DEV void p_run_body(const PRunArgs& a, int nframes, const uint8_t* __restrict
 #ifdef SO_STAMPS
             if (lane == 0 && rec) rec[10] = __builtin_amdgcn_s_memrealtime();
 #endif
-#if SO_RUN_ACQUIRE
             // consumer side of the hand-off (MI355X_MICROARCH.md, "Valid forms"): one relaxed
             // poll, ONE agent-scope acquire (invalidates this CU's L1), its completion awaited
             // before the barrier that releases the other waves to the window loads.  (A
             // stripe's planes are uncached: the neighbour's rows come from memory either way.)
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
             // the same tile of the reference frame had most of its blocks overflow the SEA bound
-            // -> this one searches dense from the start, except every SO_DENSE_PROBE-th frame,
+            // -> this one searches dense from the start, except every kDenseProbe-th frame,
             // which probes the bound again
-            if (MODE == kRunSingle && dep >= 0 && (f & (SO_DENSE_PROBE - 1)) != 0) {
+            if (MODE == kRunSingle && dep >= 0 && (f & (kDenseProbe - 1)) != 0) {
                 const uint32_t fb = (uint32_t)__builtin_amdgcn_readlane((int)raw, 9);
-                if (lane == 0) s_dense = fb >= (uint32_t)(SO_DENSE_THR * G::NBLK / 16) ? 1 : 0;
+                if (lane == 0) s_dense = fb >= (uint32_t)(kDenseThr * G::NBLK / 16) ? 1 : 0;
             }
         };
         // ptile_body's `post`: the next task's dequeue, before the tile's drain (one-GPU,
         // frame-pipeline and stripe runs)
-#ifndef SO_DEQ_LATE   // A/B builds: dequeue at the loop top, after the done flag
         const auto take_next = [&]() {
             if (wave == 0) nxt_v = run_dequeue(ws);   // waits for the tile's stores too
             nxt_taken = true;
         };
-#else
-        const NoPre take_next{};
-#endif
         const uint8_t* ref = FPIPE ? sp.land0 + (long long)(sp.gbase + f) * sp.stride
                                    : (MODE == kRunSingle || TWOP) ? a.ref[f] : (f ? a.out[f - 1].recon : ref0);
         if constexpr (TWOP) {
@@ -3754,13 +3571,11 @@ SO_DEV void p_run_body(const PRunArgs& a, int nframes, const uint8_t* __restrict
         }
     }
 }
-#ifndef SO_EP_REG
 #undef ep
-#endif
 
 #define SO_RUN_KERNEL_ATTRS(NW, VBS) \
     __launch_bounds__(NW * 64)       \
-    __attribute__((amdgpu_waves_per_eu(VBS ? SO_VBS_WPE : (NW >= 16 ? SO_PTILE_WPE16 : SO_SEA2_WPE))))
+    __attribute__((amdgpu_waves_per_eu(VBS ? kVbsWpe : (NW >= 16 ? kPtileWpe16 : kSea2Wpe))))
 template <int NW, int MODE, bool VBS = false, bool HOOKS = false, bool UQP = false, bool ZSKIP = false>
 __global__ void SO_RUN_KERNEL_ATTRS(NW, VBS)
 p_run_kernel(const PRunArgs a, int nframes, const uint8_t* __restrict__ ref0, int H, int W,
@@ -3800,10 +3615,10 @@ size_t p_run_workspace_words(int H, int W) {
 constexpr size_t kLdsPerCuObserved = 161280;   // gfx950: 3 x 53,760 B resident at once (ubench_lds_occ)
 // the VBS run holds three workgroups per CU only while its LDS (PTileLds + the kernel's few
 // scalars) stays within 53,760 B: a later LDS increase must not silently drop it to two
-static_assert(sizeof(PTileLds<Sea2GeoT<SO_PTILE_NW>, true>) + 64 <= kLdsPerCuObserved / 3,
+static_assert(sizeof(PTileLds<Sea2GeoT<kPtileNw>, true>) + 64 <= kLdsPerCuObserved / 3,
               "the VBS run's LDS no longer fits three workgroups per gfx950 CU");
 // so is the tall plain run: its 24 blocks fit only through the dword transform scratch
-static_assert(sizeof(PTileLds<RunGeoTall<SO_PTILE_NW>>) + 64 <= kLdsPerCuObserved / 3,
+static_assert(sizeof(PTileLds<RunGeoTall<kPtileNw>>) + 64 <= kLdsPerCuObserved / 3,
               "the tall plain run's LDS no longer fits three workgroups per gfx950 CU");
 static int run_shape(const void* kernel, int* ncu, int* per_cu) {
     static std::mutex mu;
@@ -3820,7 +3635,7 @@ static int run_shape(const void* kernel, int* ncu, int* per_cu) {
     if (it == cache.end()) {
         int n = 0, p = 0;
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, kernel, SO_PTILE_NW * 64, 0) != hipSuccess || p <= 0) p = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&p, kernel, kPtileNw * 64, 0) != hipSuccess || p <= 0) p = 1;
         // The occupancy API over-counts near the LDS limit on gfx950: it reports three
         // 512-thread workgroups per CU for 53,880 B of LDS, but a CU runs only two of them at
         // once (three up to 53,760 B; tools/ubench_lds_occ.cpp, profiles/r05/ubench_lds_occ.log).
@@ -3842,46 +3657,45 @@ static int run_shape(const void* kernel, int* ncu, int* per_cu) {
     return SO_OK;
 }
 
+// Every persistent-run kernel, in kRunKernels' order (so_run_select.h): entry i is the
+// instantiation its key names.  The launch, p_run_capacity and p_run_tall_choice all read this
+// table and nothing else.
+using PRunKernelFn = void (*)(const PRunArgs, int, const uint8_t*, int, int, int, const int32_t*, uint32_t*, int,
+                              const PRunStripe, double);
+template <int I>
+constexpr PRunKernelFn run_kernel_of() {
+    constexpr RunKernelKey k = kRunKernels[I];
+    static_assert(!k.tall || kRunHasTall<k.mode, k.vbs, k.hooks, k.uqp>, "48-row tiles: the plain one-GPU run only");
+    if constexpr (kRunHasTall<k.mode, k.vbs, k.hooks, k.uqp> && !k.tall)
+        return p_run_short_kernel<kPtileNw, k.slot>;
+    else
+        return p_run_kernel<kPtileNw, k.mode, k.vbs, k.hooks, k.uqp, k.slot>;
+}
+struct PRunKernel {
+    RunKernelKey key;
+    PRunKernelFn kernel;
+};
+template <int... I>
+constexpr std::array<PRunKernel, sizeof...(I)> run_kernel_table(std::integer_sequence<int, I...>) {
+    return {{{kRunKernels[I], run_kernel_of<I>()}...}};
+}
+static constexpr auto kRunTable = run_kernel_table(std::make_integer_sequence<int, kRunKernelCount>{});
+
 // Resident workgroups of the persistent run kernel on the current device (so_p_run_resident_
 // workgroups): the grid a launch uses when nothing caps it.
 // mode < 0: the smallest over every instantiation a run of that VBS setting may launch (the
 // one-GPU run with and without test hooks, the stripe, frame-pipeline and two-pass modes): the
 // ranks sharing one device size their claims by it, whichever kernel each of them launches.
 int p_run_capacity(int vbs, int mode) {
-    constexpr int NW = SO_PTILE_NW;
-    const void* ks[16];
-    int n = 0;
-    const auto add = [&](int m, const void* k) {
-        if (mode < 0 || mode == m) ks[n++] = k;
-    };
-    if (vbs) {
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, true>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, true, true>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, true, false, true>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, true, true, true>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, true, false, true, true>));
-        add(kRunFPipe, reinterpret_cast<const void*>(p_run_kernel<NW, kRunFPipe, true>));
-        add(kRunFPipe, reinterpret_cast<const void*>(p_run_kernel<NW, kRunFPipe, true, false, true>));
-    } else {
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false, true>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false, false, false, true>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_short_kernel<NW, false>));
-        add(kRunSingle, reinterpret_cast<const void*>(p_run_short_kernel<NW, true>));
-        add(kRunStripe, reinterpret_cast<const void*>(p_run_kernel<NW, kRunStripe, false>));
-        add(kRunFPipe, reinterpret_cast<const void*>(p_run_kernel<NW, kRunFPipe, false>));
-        add(kRunTwoPass, reinterpret_cast<const void*>(p_run_kernel<NW, kRunTwoPass, false>));
-        add(kRunFPipe2P, reinterpret_cast<const void*>(p_run_kernel<NW, kRunFPipe2P, false>));
-    }
-    if (n == 0) return -SO_E_INVALID;
     int best = 0;
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < kRunKernelCount; ++i) {
+        if (!run_kernel_counts(i, vbs != 0, mode)) continue;
         int ncu = 0, per_cu = 0;
-        const int rc = run_shape(ks[i], &ncu, &per_cu);
+        const int rc = run_shape(reinterpret_cast<const void*>(kRunTable[i].kernel), &ncu, &per_cu);
         if (rc != SO_OK) return -rc;
-        if (i == 0 || ncu * per_cu < best) best = ncu * per_cu;
+        if (best == 0 || ncu * per_cu < best) best = ncu * per_cu;
     }
-    return best;
+    return best > 0 ? best : SO_E_INVALID;   // no such entry
 }
 
 // The one-GPU plain run's tile (SO_OPT_RUN_TALL_TILES): 48 rows when forced, or when unset and
@@ -3894,11 +3708,10 @@ static int p_run_tall_choice(int H, int W, int conc, bool zskip, bool* tall) {
         *tall = opt != 0;
         return SO_OK;
     }
-    constexpr int NW = SO_PTILE_NW;
+    constexpr int NW = kPtileNw;
     int ncu = 0, per_cu = 0;
-    const int rc = run_shape(zskip ? reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false, false, false, true>)
-                                   : reinterpret_cast<const void*>(p_run_kernel<NW, kRunSingle, false>),
-                             &ncu, &per_cu);
+    const int tall_kernel = run_kernel_find(kRunSingle, false, false, false, zskip, true);
+    const int rc = run_shape(reinterpret_cast<const void*>(kRunTable[tall_kernel].kernel), &ncu, &per_cu);
     if (rc != SO_OK) return rc;
     using GT = RunGeoTall<NW>;
     *tall = (long long)run_tiles(H, W, GT::TBX, GT::TBY) * conc >= (long long)ncu * per_cu;
@@ -3907,7 +3720,7 @@ static int p_run_tall_choice(int H, int W, int conc, bool zskip, bool* tall) {
 int p_run_tile_rows(int H, int W, int conc) {
     bool tall = false;
     if (p_run_tall_choice(H, W, conc, false, &tall) != SO_OK) return -1;
-    return tall ? RunGeoTall<SO_PTILE_NW>::TBY : Sea2Geo::TBY;
+    return tall ? RunGeoTall<kPtileNw>::TBY : Sea2Geo::TBY;
 }
 
 // refs / deps (may be null: one run, frame g predicting from g - 1 and frame 0 from ref0): frame g
@@ -3918,41 +3731,29 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
                           const int32_t* qp_row, const PFrameOut* outs, uint32_t* ws, const PRunStripe& sp0,
                           int max_wg, hipStream_t st, const uint8_t* const* refs = nullptr,
                           const int* deps = nullptr, int conc = 1, double lam = 0.0) {
-    using GS = Sea2GeoT<SO_PTILE_NW>;
+    using GS = Sea2GeoT<kPtileNw>;
     // the test-hook instantiation (one GPU only) while SO_OPT_COUNT_SAD_OPS / _TEST_LOSE_FLAG is set
-    const bool hook_set = option(SO_OPT_COUNT_SAD_OPS) != 0 || option(SO_OPT_TEST_LOSE_FLAG) != 0;
-    if (hook_set && MODE != kRunSingle) {   // no hook instantiation here: refuse rather than ignore
+    const bool hooks = option(SO_OPT_COUNT_SAD_OPS) != 0 || option(SO_OPT_TEST_LOSE_FLAG) != 0;
+    const bool zskip = option(SO_OPT_RUN_ZERO_SKIP) != 0;
+    // the plain one-GPU run without hooks: p_run_kernel on 48-row tiles or its 32-row twin
+    bool tall = false;
+    if (MODE == kRunSingle && !VBS && !hooks) {
+        const int rc = p_run_tall_choice(H, W, conc, zskip, &tall);
+        if (rc != SO_OK) return rc;
+    }
+    // the launch's kernel (so_run_select.h); a launch whose grid has more slots than a frame has
+    // tiles may take the latency-bound twin below, the grid itself is always this one's
+    const int k0 = run_kernel_select(MODE, VBS, hooks, qp_row == nullptr, zskip, tall, false);
+    if (k0 == kRunSelectHooks) {   // no hook instantiation here: refuse rather than ignore
         set_error("p_run: SO_OPT_COUNT_SAD_OPS / SO_OPT_TEST_LOSE_FLAG apply to the one-GPU run only (so_encode_p_run, "
                   "so_encode_p_runs); this run kind has no hook instantiation");
         return SO_E_INVALID;
     }
-    const bool hooks = MODE == kRunSingle && hook_set;
-    // VBS without a row-QP schedule: the uniform-QP instantiation (p_run_kernel's UQP)
-    const bool uqp = VBS && qp_row == nullptr;
-    // the plain one-GPU run with the all-zero-wave IDCT skip (SO_OPT_RUN_ZERO_SKIP; not with hooks)
-    constexpr bool ZS_OK = MODE == kRunSingle && !VBS;
-    const bool zskip = ZS_OK && !hooks && option(SO_OPT_RUN_ZERO_SKIP) != 0;
-    // the uniform-QP VBS run's latency-bound twin (p_run_kernel's ZSKIP slot on VBS): chosen below
-    // when the grid has more slots than a frame has tiles
-    constexpr bool VL_OK = MODE == kRunSingle && VBS;
-    const bool vlat_ok = VL_OK && uqp && !hooks && SO_VBS_BALLOT_LATENCY;
-    // the plain one-GPU run without hooks: p_run_kernel on 48-row tiles or its 32-row twin
-    constexpr bool TALL_OK = MODE == kRunSingle && !VBS;
-    bool tall = false;
-    if (TALL_OK && !hooks) {
-        const int rc = p_run_tall_choice(H, W, conc, zskip, &tall);
-        if (rc != SO_OK) return rc;
+    if (k0 < 0) {
+        set_error("p_run: no kernel for run kind %d%s", MODE, VBS ? " with VBS" : "");
+        return SO_E_INVALID;
     }
-    const int tby = tall ? RunGeoTall<SO_PTILE_NW>::TBY : GS::TBY;
-    const void* const kfn =
-        TALL_OK && !hooks && !tall
-            ? (zskip ? reinterpret_cast<const void*>(p_run_short_kernel<SO_PTILE_NW, true>)
-                     : reinterpret_cast<const void*>(p_run_short_kernel<SO_PTILE_NW, false>)) :
-        hooks ? (uqp ? reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, MODE == kRunSingle, VBS>)
-                     : reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, MODE == kRunSingle>))
-              : (uqp     ? reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, false, VBS>)
-                 : zskip ? reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, false, false, ZS_OK>)
-                         : reinterpret_cast<const void*>(p_run_kernel<SO_PTILE_NW, MODE, VBS, false>));
+    const int tby = kRunTable[k0].key.tall ? RunGeoTall<kPtileNw>::TBY : GS::TBY;
     if (hooks && option(SO_OPT_TEST_LOSE_FLAG) != 0) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
@@ -3963,7 +3764,7 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
     }
     int ncu = 0, per_cu = 0;
     {
-        const int rc = run_shape(kfn, &ncu, &per_cu);
+        const int rc = run_shape(reinterpret_cast<const void*>(kRunTable[k0].kernel), &ncu, &per_cu);
         if (rc != SO_OK) return rc;
     }
     const int nbx = W / 16;
@@ -4019,33 +3820,9 @@ static int p_run_launch_t(const uint8_t* const* curs, int nframes, const uint8_t
             sp.p2lag = lag < 1 ? 1 : (lag > ntr ? ntr : lag);
         }
         const uint8_t* const r0 = f0 ? outs[f0 - 1].recon : ref0;
-#define SO_P_RUN_GO(HK, UQ, ZS)                                                                                         \
-    hipLaunchKernelGGL((p_run_kernel<SO_PTILE_NW, MODE, VBS, HK, UQ, ZS>), dim3((unsigned)grid), dim3(SO_PTILE_NW * 64), \
-                       0, st, a, n, r0, H, W, qp_rd, qp_row, ws, (int)(f0 * ntiles), sp, lam)
-        if (hooks && uqp)
-            SO_P_RUN_GO(MODE == kRunSingle, VBS, false);
-        else if (hooks)
-            SO_P_RUN_GO(MODE == kRunSingle, false, false);
-        else if (uqp && vlat_ok && ntiles < grid)
-            SO_P_RUN_GO(false, VBS, VL_OK);
-        else if (uqp)
-            SO_P_RUN_GO(false, VBS, false);
-        else if (TALL_OK && !tall) {
-            if constexpr (TALL_OK) {
-                if (zskip)
-                    hipLaunchKernelGGL((p_run_short_kernel<SO_PTILE_NW, true>), dim3((unsigned)grid),
-                                       dim3(SO_PTILE_NW * 64), 0, st, a, n, r0, H, W, qp_rd, qp_row, ws,
-                                       (int)(f0 * ntiles), sp, lam);
-                else
-                    hipLaunchKernelGGL((p_run_short_kernel<SO_PTILE_NW, false>), dim3((unsigned)grid),
-                                       dim3(SO_PTILE_NW * 64), 0, st, a, n, r0, H, W, qp_rd, qp_row, ws,
-                                       (int)(f0 * ntiles), sp, lam);
-            }
-        } else if (zskip)
-            SO_P_RUN_GO(false, false, ZS_OK);
-        else
-            SO_P_RUN_GO(false, false, false);
-#undef SO_P_RUN_GO
+        const int k = run_kernel_select(MODE, VBS, hooks, qp_row == nullptr, zskip, tall, ntiles < grid);
+        hipLaunchKernelGGL(kRunTable[k].kernel, dim3((unsigned)grid), dim3(kPtileNw * 64), 0, st, a, n, r0, H, W,
+                           qp_rd, qp_row, ws, (int)(f0 * ntiles), sp, lam);
         const int rc = check_launch("p_run_kernel");
         if (rc != SO_OK) return rc;
     }

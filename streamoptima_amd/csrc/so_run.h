@@ -3,6 +3,7 @@
 // see one definition of the kernel-argument structs.
 #pragma once
 #include "so_common.h"
+#include "so_run_select.h"
 
 namespace so {
 

@@ -337,7 +337,7 @@ def test_dense_predicted_tiles_match_per_frame(gpu, monkeypatch, content):
     the per-frame kernels (SO_PIPELINE=0: me_wave_kernel's dense search), frame by frame, with
     edge tiles (640 = 5 tiles, 272 rows).  noise_then_bench: a scene change at frame 9 to
     textured content, the tiles still predicted dense until the probe frame (every 16th,
-    SO_DENSE_PROBE), over 20 frames."""
+    kDenseProbe), over 20 frames."""
     from streamoptima_amd.Encoder import Y_Video_codec
     from streamoptima_amd.digest import symbols_digest
     from streamoptima_amd.engine import alloc_planes

@@ -201,3 +201,21 @@ def test_device_dct_header_bitwise_vs_oracle(tmp_path):
                     f"-Wl,-rpath,{libdir}", "-o", exe], check=True, capture_output=True)
     r = subprocess.run([exe, "300000"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_run_kernel_selection_truth_table(tmp_path):
+    """streamoptima_amd/csrc/so_run_select.h (which persistent-run instantiation a launch uses)
+    compiled alone for the host gives, for every combination of its inputs, the entry written out
+    in tests/host/run_select_check.cpp; every entry is reachable and the capacity filters count
+    9 plain and 7 VBS entries."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx is not None, "no host C++ compiler"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "run_select_check")
+    subprocess.run([cxx, "-O1", "-std=c++17", "-Wall", "-Werror",
+                    os.path.join(root, "tests", "host", "run_select_check.cpp"), "-o", exe],
+                   check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr

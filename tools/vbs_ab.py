@@ -1,7 +1,7 @@
 """VBSEnable persistent-run A/B: per-frame time of the 4K / 1088p VBS P-run (p_run_kernel<8, 0,
 true>) for the product library and the builds named on the command line (SO_LIB_PATH), each in
 a fresh process, plus the count of blocks that took the dense search.
-    python tools/vbs_ab.py tools/_ab/vbsdense.so"""
+    python tools/vbs_ab.py tools/_ab/x.so"""
 import json
 import os
 import subprocess
