@@ -11,6 +11,7 @@
 #pragma once
 #include "so_common.h"
 #include "so_dct.h"
+#include "so_dpp.h"
 
 namespace so {
 
@@ -159,6 +160,42 @@ SO_DEV void load_row_i16(const int16_t* __restrict__ p, int* v) {
         v[2 * k] = (int)(int16_t)(w[k] & 0xFFFF);
         v[2 * k + 1] = (int)(int16_t)(w[k] >> 16);
     }
+}
+
+// ---- packed 16-pixel rows (tq16_exact's FAST tail) -------------------------------------------
+// The reconstruction row written in place: byte e of pw[k] (the prediction) becomes
+// (prediction + (g[4 k + e] >> 24)) & 255, one SDWA byte add per pixel, the other bytes of the
+// dword kept (dst_unused:UNUSED_PRESERVE).  No mask, shift or OR per pixel, and the four dwords
+// are the row store's operand as they stand.  One block in a fixed order: an SDWA write with a
+// byte dst_sel must be one wait state away from a VALU read of its register (gfx940+), which
+// the hazard recogniser does not see inside inline assembly -- here four instructions separate
+// two writes of one dword, and the s_nop covers the first reader after the block.
+#define SO_RP(k, e, g)                                                                              \
+    "v_add_u32_sdwa %" #k ", %" #k ", %" #g " dst_sel:BYTE_" #e " dst_unused:UNUSED_PRESERVE src0_sel:BYTE_" #e \
+    " src1_sel:BYTE_3\n\t"
+SO_DEV void recon_row_bytes(uint32_t (&pw)[4], const uint32_t (&g)[16]) {
+    asm(SO_RP(0, 0, 4) SO_RP(1, 0, 8) SO_RP(2, 0, 12) SO_RP(3, 0, 16)
+        SO_RP(0, 1, 5) SO_RP(1, 1, 9) SO_RP(2, 1, 13) SO_RP(3, 1, 17)
+        SO_RP(0, 2, 6) SO_RP(1, 2, 10) SO_RP(2, 2, 14) SO_RP(3, 2, 18)
+        SO_RP(0, 3, 7) SO_RP(1, 3, 11) SO_RP(2, 3, 15) SO_RP(3, 3, 19) "s_nop 0"
+        : "+v"(pw[0]), "+v"(pw[1]), "+v"(pw[2]), "+v"(pw[3])
+        : "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]), "v"(g[6]), "v"(g[7]), "v"(g[8]),
+          "v"(g[9]), "v"(g[10]), "v"(g[11]), "v"(g[12]), "v"(g[13]), "v"(g[14]), "v"(g[15]));
+}
+#undef SO_RP
+
+// sum of (c - r)^2 over 16 pixels from the packed rows: c.c - 2 c.r + r.r, twelve v_dot4_u32_u8.
+// Exact in u32: each of the three sums is at most 16 * 255^2.
+SO_DEV int sse_row_packed(const uint32_t* c, const uint32_t (&r)[4]) {
+    uint32_t sq = 0, cr = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t cw = c[k];
+        sq = __builtin_amdgcn_udot4(cw, cw, sq, false);
+        sq = __builtin_amdgcn_udot4(r[k], r[k], sq, false);
+        cr = __builtin_amdgcn_udot4(cw, r[k], cr, false);
+    }
+    return (int)(sq - 2u * cr);
 }
 
 // ---- 2-D transforms through LDS --------------------------------------------------------------
@@ -514,7 +551,9 @@ SO_DEV void dequant_row_int(const int* q, int row, int qp, int* dq) {
 //                      M_0 bit k+1) and end (N-1, k-N+1) -> start (k-N+2, N-1) for k >= N-1
 //                      (lane m = k-N+2 >= 1: M_{N-1} bit m-1 vs M_m bit N-1).
 // Registers only: no LDS, no barrier.  `flags` is unused (kept for the call sites).
-template <int N>
+// ROWSUM (N = 16): the final sum over the block's lanes by DPP (row_sum_u32) instead of
+// group_sum's four ds_bpermute steps and their lane indices.
+template <int N, bool ROWSUM = false>
 SO_DEV int block_tokens(uint8_t* flags, int l, const int* q) {
     (void)flags;
     uint32_t m = 0;
@@ -541,7 +580,12 @@ SO_DEV int block_tokens(uint8_t* flags, int l, const int* q) {
         tr += (int)((m & 1u) ^ ((m0 >> (l + 1)) & 1u));
     }
     if (l >= 1) tr += (int)(((mlast >> (l - 1)) & 1u) ^ ((m >> (N - 1)) & 1u));
-    return group_sum<N>(__builtin_popcount(m) + tr) + 1;
+    if constexpr (ROWSUM) {
+        static_assert(N == 16, "a DPP row is 16 lanes");
+        return (int)row_sum_u32((uint32_t)(__builtin_popcount(m) + tr)) + 1;
+    } else {
+        return group_sum<N>(__builtin_popcount(m) + tr) + 1;
+    }
 }
 
 // Token counts of the four 8x8 sub-blocks (16 lanes, lane l owns sub j = l>>2, rows

@@ -1800,7 +1800,7 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
         const auto derive = [&]() {
             if constexpr (FAST) {
                 asm volatile("" : "+v"(g), "+v"(l));
-                const int gbx2 = bx0 + g % TBX, gby2 = byt0 + g / TBX;
+                const int gbx2 = bx0 + (int)((uint32_t)g % TBX), gby2 = byt0 + (int)((uint32_t)g / TBX);
                 b = (size_t)(gby2 - by0) * nbx + gbx2;
                 x = gbx2 * 16;
                 y = gby2 * 16;
@@ -1809,7 +1809,7 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
         };
         const auto rows_of = [&](int g2, int l2, int& prow2, int& pcol2, const uint32_t*& crow2) {
             asm volatile("" : "+v"(g2), "+v"(l2));
-            const int bxl2 = g2 % TBX, byl2 = g2 / TBX;
+            const int bxl2 = (int)((uint32_t)g2 % TBX), byl2 = (int)((uint32_t)g2 / TBX);   // g >= 0: no sign fix-up
             lds_vu32p mp = (lds_vu32p)reinterpret_cast<const uint32_t*>(&S.mer[g2]);
             const uint32_t w0 = mp[0];
             prow2 = byl2 * 16 + SR + ((int)w0 >> 16) + l2;
@@ -1932,7 +1932,7 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
         }
         SO_MARK(tq_tokens);
         derive();
-        const int tok = block_tokens<16>(nullptr, l, q);
+        const int tok = block_tokens<16, FAST>(nullptr, l, q);
         if constexpr (TOK) {   // pass 1 of two-pass RC: the token count is all that is used
             if (l == 0) o.tokens[b] = tok;
             return;
@@ -1941,13 +1941,20 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
         store_row_i16<16>(o.qtc + b * 256 + l * 16, q);
         // the reconstruction row's store (write-through, plus the neighbours' halo rows) and
         // its SSE: the tail of both paths below
-        const auto finish = [&](const int (&rec)[16]) -> int {
+        // FAST: `rec` is the row as its four packed dwords (recon_row_bytes), the store's operand
+        // as it stands and the SSE's; every other kernel passes the sixteen pixels as ints
+        static_assert(!FAST || SC1, "the packed row goes to the write-through store");
+        const auto finish = [&](const auto& rec) -> int {
             if constexpr (SC1) {
                 so_v4u v;
+                if constexpr (FAST) {
+                    v = so_v4u{rec[0], rec[1], rec[2], rec[3]};
+                } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    v[k] = (uint32_t)(rec[4 * k] & 255) | ((uint32_t)(rec[4 * k + 1] & 255) << 8) |
-                           ((uint32_t)(rec[4 * k + 2] & 255) << 16) | ((uint32_t)(rec[4 * k + 3] & 255) << 24);
+                    for (int k = 0; k < 4; ++k)
+                        v[k] = (uint32_t)(rec[4 * k] & 255) | ((uint32_t)(rec[4 * k + 1] & 255) << 8) |
+                               ((uint32_t)(rec[4 * k + 2] & 255) << 16) | ((uint32_t)(rec[4 * k + 3] & 255) << 24);
+                }
                 uint8_t* rp = o.recon + (size_t)(y + l) * W + x;
                 asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(rp), "v"(v) : "memory");
                 if constexpr (HALO) {
@@ -1976,16 +1983,20 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
                     asm volatile("" : "+v"(g2), "+v"(l2));
                     crow2 = S.curt + ((g2 / TBX) * 16 + l2) * G::CPD + (g2 % TBX) * 4;
                 }
+                if constexpr (FAST) {
+                    e2 = sse_row_packed(crow2, rec);
+                } else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t cw = crow2[k];
+                    for (int k = 0; k < 4; ++k) {
+                        const uint32_t cw = crow2[k];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int d = (int)((cw >> (8 * e)) & 255) - (rec[4 * k + e] & 255);
-                        e2 += d * d;
+                        for (int e = 0; e < 4; ++e) {
+                            const int d = (int)((cw >> (8 * e)) & 255) - (rec[4 * k + e] & 255);
+                            e2 += d * d;
+                        }
                     }
                 }
-                e2 = group_sum<16>(e2);
+                if constexpr (FAST) e2 = (int)row_sum_u32((uint32_t)e2); else e2 = group_sum<16>(e2);
             }
             return e2;
         };
@@ -2015,12 +2026,21 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
                     rec[c] = (int)((pw[c >> 2] >> (8 * (c & 3))) & 255) +
                              (int)(uint32_t)__builtin_bit_cast(uint64_t, rd[c] + kRne);
             }
-            return finish(rec);
+            if constexpr (FAST) {   // the rare path packs its row once, for the same tail
+                uint32_t v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    v[k] = (uint32_t)(rec[4 * k] & 255) | ((uint32_t)(rec[4 * k + 1] & 255) << 8) |
+                           ((uint32_t)(rec[4 * k + 2] & 255) << 16) | ((uint32_t)(rec[4 * k + 3] & 255) << 24);
+                return finish(v);
+            } else {
+                return finish(rec);
+            }
         };
         const auto full = [&]() -> int {
             if constexpr (FAST) {
                 {
-                    int dq[16], rec[16];
+                    int dq[16];
                     double rd[16];
                     {   // k = qp + e(l + c) by the same row shift as the quantiser's scale
                         int k = qpr + (l == 15 ? 1 : 0);
@@ -2039,26 +2059,28 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
                     SO_MARK(tq_recon);
                     derive();
                     // v + kFix holds round(v 2^24) + 2^23 in its low mantissa dword: bits 24.. are
-                    // floor(v + 1/2) (mod 256 with the prediction added above them: only rec & 255
-                    // is used), and the low 24 bits within 2 of 0 (mod 2^24) mean v is within
-                    // kFastDeltaInv = 1.5 x 2^-24 of a half-integer
+                    // floor(v + 1/2) mod 256: that top byte added to the prediction's byte, mod 256,
+                    // is the pixel (only rec & 255 is used), written in place into the prediction
+                    // dwords (recon_row_bytes).  The low 24 bits within 2 of 0 (mod 2^24) mean v is
+                    // within kFastDeltaInv = 1.5 x 2^-24 of a half-integer
                     constexpr double kFix = 0x1.8p28 + 0.5;
                     uint32_t mn = 0xFFFFFFFFu;
+                    uint32_t pw[4];
                     {
                         int prow2, pcol2;
                         const uint32_t* crow2;
                         rows_of(g, l, prow2, pcol2, crow2);
-                        uint32_t pw[4];
                         win_row16<G::RP>(S.win, prow2, pcol2, pw);
+                        uint32_t gfix[16];
 #pragma unroll
                         for (int c = 0; c < 16; ++c) {
-                            const uint32_t gfix = (uint32_t)__builtin_bit_cast(uint64_t, rd[c] + kFix);
-                            rec[c] = (int)(((((pw[c >> 2] >> (8 * (c & 3))) & 255u) << 24) + gfix) >> 24);
-                            const uint32_t t = (gfix + 2u) << 8;
+                            gfix[c] = (uint32_t)__builtin_bit_cast(uint64_t, rd[c] + kFix);
+                            const uint32_t t = (gfix[c] + 2u) << 8;
                             mn = t < mn ? t : mn;
                         }
+                        recon_row_bytes(pw, gfix);
                     }
-                    if (__builtin_amdgcn_ballot_w64(mn <= (4u << 8)) == 0) return finish(rec);
+                    if (__builtin_amdgcn_ballot_w64(mn <= (4u << 8)) == 0) return finish(pw);
                 }
                 SO_MARK(tq_inv_fallback);
                 const uint64_t act = __builtin_amdgcn_ballot_w64(true);
@@ -2079,12 +2101,16 @@ SO_DEV void tq16_exact(PTileLds<G, false, HALFTQ>& S, int g, int l, double* scra
             // for content where most blocks quantise to zero: in the default kernel the branch
             // cost two spills and +0.3-0.5 % on textured content
             if (__builtin_amdgcn_ballot_w64(tok != 1) == 0) {
-                int rec[16];
                 uint32_t pw[4];
                 win_row16<G::RP>(S.win, prow, pcol, pw);
+                if constexpr (FAST) {
+                    sse = finish(pw);
+                } else {
+                    int rec[16];
 #pragma unroll
-                for (int c = 0; c < 16; ++c) rec[c] = (int)((pw[c >> 2] >> (8 * (c & 3))) & 255);
-                sse = finish(rec);
+                    for (int c = 0; c < 16; ++c) rec[c] = (int)((pw[c >> 2] >> (8 * (c & 3))) & 255);
+                    sse = finish(rec);
+                }
             } else {
                 sse = full();
             }
