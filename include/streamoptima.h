@@ -744,6 +744,67 @@ int so_unpack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t
                           uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc,
                           int32_t* err, void* stream);
 
+/*
+ * The chroma coefficients (so_chroma_encode_frame's qtc_u / qtc_v, device int16 [nb][64] each,
+ * row-major) as a packed stream, in both codings of the luma stream.  The models are in
+ * tests/packchromaref.py; host decoders: bitstream.unpack_chroma_frame / unpack_chroma_frame_bits.
+ *
+ * One record per luma block b, in raster order: the token list of U's 8x8 block b, then the
+ * token list of V's block b.  A list is exactly a (sub-)block list of the luma format: scan in
+ * scan_order(8); "-L" is followed by L values; "Z" > 0 is a run of Z zeros; "0" is the trailing
+ * zero run; a list also ends after 64 coefficients.  No split flag and no motion vectors.
+ *
+ * Coding "varint" (so_pack_chroma_frames): every number a zigzag LEB128 varint; the shortest
+ * record is 2 bytes.  Malformed to a decoder (k: the coefficients of the list covered so far):
+ *   * a varint running past 5 bytes or off the end of the record;
+ *   * a decoded zigzag value of 2^16 or more;
+ *   * a token -L with L < 1 or L > 64 - k;  a token Z > 64 - k;
+ *   * bytes left after V's list;
+ *   * offs[b+1] < offs[b].
+ * Accepted though never written: an over-long varint of up to 5 bytes whose value fits; a 0
+ * value inside a -L list; a run reaching exactly 64 written as Z.
+ *
+ * Coding "bits" (so_pack_chroma_frames_bits): bits MSB-first; first k in 2 bits, the order of
+ * this record's coefficient codes, shared by both lists; then U's list, then V's, tokens se and
+ * coefficient values se_k (defined above); then zero bits up to the byte boundary.  Canonical
+ * k: the k in 0..3 that minimises the record's total coefficient bits over both lists; ties go
+ * to the smallest k; a record with no coefficient writes 0.  Malformed to a decoder:
+ *   * a ue prefix of more than 16 zero bits;  a decoded z > 65535;
+ *   * a code running past the record's last byte;
+ *   * a token breaking the token rules above;
+ *   * 8 or more bits left after V's list, or any set bit among the bits left;
+ *   * offs[b+1] < offs[b].
+ * Accepted though never written: a non-minimal k; k != 0 with no coefficient; a 0 value inside
+ * a -L list; a run reaching exactly 64 written as Z.
+ *
+ * so_pack_chroma_bound(nb) = nb * 600 (two lists of 3 * (64 + 32 + 4) bytes) and
+ * so_pack_chroma_bits_bound(nb) = nb * ceil((2 + 2 * (33*64 + 19*36)) / 8) = nb * 700: loose on
+ *   purpose, like the luma bounds; a record's length fits a container's u16.  0 for nb <= 0.
+ * so_pack_chroma_frames / _bits: offs, out, cap and totals exactly as so_pack_frames_ex
+ *   (exclusive offsets with the total in offs[i][nb]; a record that would pass `cap` is not
+ *   written; totals, which may be NULL, stored at system scope).  A NULL required pointer or
+ *   nb <= 0 is SO_E_INVALID; nframes = 0 is SO_OK.  Stream-ordered, no host synchronisation.
+ * so_unpack_chroma_frames / _bits: the inverse, as so_unpack_frames: every record decoded from
+ *   exactly its bytes [offs[b], offs[b+1]) into the zeroed blocks; malformed input sets the
+ *   device int32 *err to 1 + a bad record's index (zero it first); a bad record's outputs are
+ *   unspecified.  Offsets that point outside packed[i]'s buffer are a caller precondition.
+ */
+size_t so_pack_chroma_bound(int nb);
+size_t so_pack_chroma_bits_bound(int nb);
+int so_pack_chroma_frames(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v,
+                          int nb, uint32_t* const* offs, uint8_t* const* out,
+                          unsigned long long cap, uint32_t* totals, void* stream);
+int so_pack_chroma_frames_bits(int nframes, const int16_t* const* qtc_u,
+                               const int16_t* const* qtc_v, int nb, uint32_t* const* offs,
+                               uint8_t* const* out, unsigned long long cap, uint32_t* totals,
+                               void* stream);
+int so_unpack_chroma_frames(int nframes, const uint8_t* const* packed, const uint32_t* const* offs,
+                            int nb, int16_t* const* qtc_u, int16_t* const* qtc_v, int32_t* err,
+                            void* stream);
+int so_unpack_chroma_frames_bits(int nframes, const uint8_t* const* packed,
+                                 const uint32_t* const* offs, int nb, int16_t* const* qtc_u,
+                                 int16_t* const* qtc_v, int32_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -695,16 +695,30 @@ class Y_Video_codec(BlockAPI):
         RLE token lists packed on the GPU, far smaller than the int16 QTC and the text lines).
         coding "varint": so_pack_frames, every number a varint; "bits": so_pack_frames_bits,
         Exp-Golomb codes, about half the bytes.  decoder.decode_packed_file reads either.
+        The per-block QP maps of ROI / two-pass rate control travel with their frames (container
+        layout 1).  Luma only: a chroma codec writes its GOP with transmit_packed420.
         Returns the file size in bytes."""
         if self.chroma:
-            raise NotImplementedError("the packed container carries luma only: chroma is not built there "
-                                      "(use transmit_bitstream with chroma_residual_file)")
-        if not self.encoded_package_f or self._symbols is None:
+            raise NotImplementedError("transmit_packed writes luma only: a chroma=True codec writes luma, chroma "
+                                      "and QP maps with transmit_packed420")
+        return self._write_packed(path, coding, None)
+
+    def transmit_packed420(self, path: str, coding: str = "varint") -> int:
+        """transmit_packed for a chroma=True codec: luma, the chroma coefficients
+        (so_pack_chroma_frames, or so_pack_chroma_frames_bits with coding "bits") and the QP maps,
+        if any, in one file (packedfile.py layout 1).  decoder.decode_packed_file rebuilds Y, U
+        and V from it.  Returns the file size in bytes."""
+        if not self.chroma:
+            raise ValueError("transmit_packed420 needs chroma=True (transmit_packed writes a luma-only GOP)")
+        return self._write_packed(path, coding, True)
+
+    def _write_packed(self, path: str, coding: str, chroma) -> int:
+        if not self.encoded_package_f or self._symbols is None or (chroma and self.chroma_symbols is None):
             print("[ERROR] No encoded package available, please run encode() first")
             return 0
         from . import packedfile
         return packedfile.write(path, self.engine(), self._symbols, self.encoded_package["Qp_per_row_per_frame"],
-                                coding=coding)
+                                coding=coding, chroma_symbols=self.chroma_symbols if chroma else None)
 
     def transmit_bitstream(self, intra_dur=None, block_size=None, mv_file=None, residual_file=None,
                            qp_map_file=None, chroma_residual_file=None):

@@ -372,6 +372,113 @@ def unpack_frame_bits(buf, nb: int, bs: int, frame_type: int) -> dict:
     return {"split": split, "mv": mv, "qtc": qtc}
 
 
+# ---- packed chroma stream (so_pack_chroma_frames / so_pack_chroma_frames_bits) -------------------
+def _chroma_lists(nb: int, token, coef, end_of_record) -> dict:
+    """nb records of two 8x8 token lists (U's, then V's) read through token() / coef();
+    end_of_record(b) runs after V's list."""
+    q = np.zeros((2, nb, 64), dtype=np.int16)
+    order = scan_order(8)
+    for b in range(nb):
+        for j in range(2):
+            k = 0
+            while k < 64:
+                t = token()
+                if t < 0:
+                    if -t > 64 - k:
+                        raise ValueError(f"record {b}: a list of {-t} values at position {k} of 64")
+                    q[j, b, order[k:k - t]] = [coef() for _ in range(-t)]
+                    k -= t
+                elif t == 0:
+                    break
+                else:
+                    if t > 64 - k:
+                        raise ValueError(f"record {b}: a run of {t} zeros at position {k} of 64")
+                    k += t
+        end_of_record(b)
+    return {"qtc_u": q[0], "qtc_v": q[1]}
+
+
+def unpack_chroma_frame(buf, nb: int) -> dict:
+    """One frame's packed chroma stream in the varint coding (so_pack_chroma_frames; the format is
+    in include/streamoptima.h) -> {"qtc_u", "qtc_v"}, int16 [nb, 64] each.  Raises ValueError on
+    malformed input, by the rules of so_unpack_chroma_frames: a varint running past 5 bytes or off
+    the end, a zigzag value of 2^16 or more, a token -L with L > 64 - k or Z > 64 - k, bytes left
+    after the last record's V list.  Record boundaries are not known here (no offsets), so a
+    varint or a list running from one record into the next is seen only where parsing stops."""
+    va = varints(buf)
+    if va.size and (int(va.min()) < -32768 or int(va.max()) > 32767):
+        raise ValueError("a value outside int16 in the packed chroma stream")
+    v = va.tolist()
+    p = 0
+
+    def nxt() -> int:
+        nonlocal p
+        if p >= len(v):
+            raise ValueError("packed chroma stream ends inside a record")
+        p += 1
+        return v[p - 1]
+
+    out = _chroma_lists(nb, nxt, nxt, lambda b: None)
+    if p != len(v):
+        raise ValueError(f"{len(v) - p} values after the last record")
+    return out
+
+
+def unpack_chroma_frame_bits(buf, nb: int) -> dict:
+    """One frame's packed chroma stream in the "bits" coding (so_pack_chroma_frames_bits) ->
+    {"qtc_u", "qtc_v"} as unpack_chroma_frame.  Parses sequentially and skips to the next byte
+    boundary after each record, so it needs no offsets.  Raises ValueError on malformed input, by
+    the rules of so_unpack_chroma_frames_bits: a ue prefix of more than 16 zero bits, a decoded
+    z > 65535, a code running past the last byte, the token rules of unpack_chroma_frame, a set
+    pad bit, bytes after the last record."""
+    data = bytes(np.asarray(buf, dtype=np.uint8).reshape(-1))
+    nbits = 8 * len(data)
+    pos = 0
+    kk = 0
+
+    def peek(n: int) -> int:
+        by = pos >> 3
+        w = int.from_bytes(data[by:by + 8].ljust(8, b"\0"), "big")
+        return (w >> (64 - (pos & 7) - n)) & ((1 << n) - 1)
+
+    def take(n: int) -> int:
+        nonlocal pos
+        if pos + n > nbits:
+            raise ValueError("packed chroma stream ends inside a code")
+        v = peek(n)
+        pos += n
+        return v
+
+    def ue(k: int = 0) -> int:
+        zeros = 17 - peek(17).bit_length()       # zeros past the end: caught by take
+        if zeros > 16:
+            raise ValueError("a prefix of more than 16 zero bits in the packed chroma stream")
+        z = take(2 * zeros + 1 + k) - (1 << k)
+        if z > 65535:
+            raise ValueError("a value outside int16 in the packed chroma stream")
+        return (z >> 1) ^ -(z & 1)
+
+    def token() -> int:
+        return ue()
+
+    def coef() -> int:
+        return ue(kk)
+
+    def end_of_record(b: int) -> None:
+        nonlocal kk
+        if take(-pos % 8):
+            raise ValueError(f"record {b}: a set bit in the padding")
+        if b + 1 < nb:
+            kk = take(2)
+
+    if nb > 0:
+        kk = take(2)
+    out = _chroma_lists(nb, token, coef, end_of_record)
+    if pos != nbits:
+        raise ValueError(f"{(nbits - pos) // 8} bytes after the last record")
+    return out
+
+
 # ---- chroma residual line (build extension: chroma 4:2:0) ------------------------------------------
 def chroma_residual_line(u_blocks, v_blocks) -> str:
     """One frame's chroma coefficients: U's entropy_encoder_frame line at block size 8, '|', V's

@@ -74,6 +74,23 @@ size_t pack_bits_block_bound(int bs);   // so_packbits.hip
 int unpack_bits_frames_launch(const UnpackFrame* frames, int nframes, int nb, int bs, int32_t* err, hipStream_t st);
 int pack_bits_frames_launch(const PackFrame* frames, int nframes, int nb, int bs, unsigned long long cap,
                             uint32_t* totals, hipStream_t st);
+struct ChromaPackFrame {   // so_packchroma.hip
+    const int16_t* qu;
+    const int16_t* qv;
+    uint32_t* offs;
+    uint8_t* out;
+};
+struct ChromaUnpackFrame {
+    const uint8_t* in;
+    const uint32_t* offs;
+    int16_t* qu;
+    int16_t* qv;
+};
+size_t pack_chroma_record_bound(bool bits);
+int pack_chroma_frames_launch(const ChromaPackFrame* frames, int nframes, int nb, bool bits, unsigned long long cap,
+                              uint32_t* totals, hipStream_t st);
+int unpack_chroma_frames_launch(const ChromaUnpackFrame* frames, int nframes, int nb, bool bits, int32_t* err,
+                                hipStream_t st);
 int stripe_halo_push_launch(const uint8_t* plane, int W, int by0, int by1, uint8_t* up, uint8_t* dn,
                             uint32_t* up_flags, uint32_t* dn_flags, int gf, uint32_t epoch, hipStream_t st);
 int frame_push_launch(const uint8_t* plane, int H, int W, uint8_t* dst, uint32_t* flags, uint32_t epoch,
@@ -1403,6 +1420,68 @@ int so_unpack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t
                           int16_t* const* qtc, int32_t* err, void* stream) {
     return unpack_frames_any("so_unpack_frames_bits", true, nframes, frame_types, packed, offs, nb, bs, split, mv, qtc,
                              err, stream);
+}
+
+// ---- the chroma coefficients as a packed stream, both codings (so_packchroma.hip) ------------
+size_t so_pack_chroma_bound(int nb) { return nb <= 0 ? 0 : (size_t)nb * pack_chroma_record_bound(false); }
+size_t so_pack_chroma_bits_bound(int nb) { return nb <= 0 ? 0 : (size_t)nb * pack_chroma_record_bound(true); }
+
+static int pack_chroma_any(const char* fn, bool bits, int nframes, const int16_t* const* qtc_u,
+                           const int16_t* const* qtc_v, int nb, uint32_t* const* offs, uint8_t* const* out,
+                           unsigned long long cap, uint32_t* totals, void* stream) {
+    if (nb <= 0 || nframes < 0) {
+        set_error("%s: nb %d / nframes %d", fn, nb, nframes);
+        return SO_E_INVALID;
+    }
+    if (nframes == 0) return SO_OK;
+    SO_NEED(qtc_u, fn); SO_NEED(qtc_v, fn); SO_NEED(offs, fn); SO_NEED(out, fn);
+    std::vector<ChromaPackFrame> fr((size_t)nframes);
+    for (int i = 0; i < nframes; ++i) {
+        SO_NEED(qtc_u[i], fn); SO_NEED(qtc_v[i], fn); SO_NEED(offs[i], fn); SO_NEED(out[i], fn);
+        fr[i] = ChromaPackFrame{qtc_u[i], qtc_v[i], offs[i], out[i]};
+    }
+    return pack_chroma_frames_launch(fr.data(), nframes, nb, bits, cap, totals, (hipStream_t)stream);
+}
+
+static int unpack_chroma_any(const char* fn, bool bits, int nframes, const uint8_t* const* packed,
+                             const uint32_t* const* offs, int nb, int16_t* const* qtc_u, int16_t* const* qtc_v,
+                             int32_t* err, void* stream) {
+    if (nb <= 0 || nframes < 0) {
+        set_error("%s: nb %d / nframes %d", fn, nb, nframes);
+        return SO_E_INVALID;
+    }
+    if (nframes == 0) return SO_OK;
+    SO_NEED(packed, fn); SO_NEED(offs, fn); SO_NEED(qtc_u, fn); SO_NEED(qtc_v, fn); SO_NEED(err, fn);
+    std::vector<ChromaUnpackFrame> fr((size_t)nframes);
+    for (int i = 0; i < nframes; ++i) {
+        SO_NEED(packed[i], fn); SO_NEED(offs[i], fn); SO_NEED(qtc_u[i], fn); SO_NEED(qtc_v[i], fn);
+        fr[i] = ChromaUnpackFrame{packed[i], offs[i], qtc_u[i], qtc_v[i]};
+    }
+    return unpack_chroma_frames_launch(fr.data(), nframes, nb, bits, err, (hipStream_t)stream);
+}
+
+int so_pack_chroma_frames(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
+                          uint32_t* const* offs, uint8_t* const* out, unsigned long long cap, uint32_t* totals,
+                          void* stream) {
+    return pack_chroma_any("so_pack_chroma_frames", false, nframes, qtc_u, qtc_v, nb, offs, out, cap, totals, stream);
+}
+
+int so_pack_chroma_frames_bits(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
+                               uint32_t* const* offs, uint8_t* const* out, unsigned long long cap, uint32_t* totals,
+                               void* stream) {
+    return pack_chroma_any("so_pack_chroma_frames_bits", true, nframes, qtc_u, qtc_v, nb, offs, out, cap, totals,
+                           stream);
+}
+
+int so_unpack_chroma_frames(int nframes, const uint8_t* const* packed, const uint32_t* const* offs, int nb,
+                            int16_t* const* qtc_u, int16_t* const* qtc_v, int32_t* err, void* stream) {
+    return unpack_chroma_any("so_unpack_chroma_frames", false, nframes, packed, offs, nb, qtc_u, qtc_v, err, stream);
+}
+
+int so_unpack_chroma_frames_bits(int nframes, const uint8_t* const* packed, const uint32_t* const* offs, int nb,
+                                 int16_t* const* qtc_u, int16_t* const* qtc_v, int32_t* err, void* stream) {
+    return unpack_chroma_any("so_unpack_chroma_frames_bits", true, nframes, packed, offs, nb, qtc_u, qtc_v, err,
+                             stream);
 }
 
 }  // extern "C"

@@ -267,17 +267,37 @@ class decoder:
         return host
 
     def decode_packed_file(self, path: str, save_decoded_frames=True):
-        """Encoder.transmit_packed's file: the packed streams go to the GPU, so_unpack_frames (or
-        so_unpack_frames_bits, by the file's version) restores split / mv / qtc of every block
-        in parallel, and the frames are rebuilt by the same kernels as decode()."""
+        """Encoder.transmit_packed's or transmit_packed420's file (packedfile.py, both layouts): the
+        packed streams go to the GPU, so_unpack_frames (or so_unpack_frames_bits, by the file's
+        coding) restores split / mv / qtc of every block in parallel, and the frames are rebuilt
+        by the same kernels as decode().  Per-block QP maps in the file are applied.  With chroma
+        in the file so_unpack_chroma_frames (_bits) restores the coefficients and U and V are
+        rebuilt too (self.decoded_chroma, save_yuv420)."""
         from . import packedfile
         eng = self._eng()
         meta = packedfile.read(path, eng.device)
         if (meta["h"], meta["w"], meta["bs"], meta["nb"]) != (eng.h, eng.w, eng.bs, eng.nb):
             raise ValueError(f"{path}: {meta['w']}x{meta['h']} bs {meta['bs']} does not match this decoder")
+        chroma = meta["chroma_packed"] is not None
+        if chroma and self.FMEEnable:
+            raise NotImplementedError("chroma with FMEEnable is not built")
+        if chroma and self.block_size != 16:
+            raise NotImplementedError("chroma needs block_size 16")
         syms = eng.unpack_symbols(meta["frame_types"], meta["packed"], meta["offs"], coding=meta["coding"])
         for s, q in zip(syms, meta["qp_rows"]):
             s.qp_row = q or None
+        for s, m in zip(syms, meta["qp_maps"] or []):
+            if m is not None:
+                s.extra["qp_map"] = m
+        if chroma:
+            qtcs = eng.unpack_chroma_symbols(meta["chroma_packed"], meta["chroma_offs"], coding=meta["coding"])
+            lum = [FrameSymbols(s.frame_type, s.split, s.mv, None, None, None, None, qp_rd=self.Qp,
+                                qp_row=s.qp_row if self._rc() else None,
+                                extra={"qp_map": s.extra["qp_map"]} if "qp_map" in s.extra else {}) for s in syms]
+            dev = self._chroma_loop(eng, lum, qtcs, int(meta["chroma_qp_offset"]))
+            h2, w2 = self.h_pixels // 2, self.w_pixels // 2
+            self.decoded_chroma_device = dev
+            self.decoded_chroma = [(u.cpu().numpy()[:h2, :w2], v.cpu().numpy()[:h2, :w2]) for u, v in dev]
         decoded = self.decode_symbols(syms, eng)
         host = [d.cpu().numpy()[: self.h_pixels, : self.w_pixels] for d in decoded]
         if save_decoded_frames:

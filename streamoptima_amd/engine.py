@@ -667,6 +667,70 @@ class Engine:
             raise ValueError(f"{name}: malformed packed stream at block {bad - 1}")
         return syms
 
+    # ---- packed chroma stream (so_pack_chroma_frames / so_pack_chroma_frames_bits) ------------
+    def pack_chroma_bound(self, coding: str = "varint") -> int:
+        bound = self.lib.so_pack_chroma_bits_bound if pack_coding_is_bits(coding) else self.lib.so_pack_chroma_bound
+        return int(bound(self.nb))
+
+    def pack_chroma_symbols(self, csyms: list, offs: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                            totals: torch.Tensor | None = None, coding: str = "varint"):
+        """Each frame's chroma coefficients (ChromaSymbols.qtc_u / .qtc_v) as one packed byte stream
+        on the device (include/streamoptima.h so_pack_chroma_frames); asynchronous.  Returns (offs
+        int32 [n, nb + 1], out uint8 [n, cap]) as pack_symbols does: frame i's stream is
+        out[i, :offs[i, nb]], record b starts at offs[i, b].  The default capacity never overflows.
+        totals: a device int32 [n] that also receives offs[i, nb].  coding: "varint" or "bits"."""
+        bits = pack_coding_is_bits(coding)
+        n, nb = len(csyms), self.nb
+        if n == 0:
+            raise ValueError("pack_chroma_symbols: no frames")
+        for c in csyms:
+            for t in (c.qtc_u, c.qtc_v):
+                if t.dtype != torch.int16 or t.numel() != nb * 64 or t.device != self.device or not t.is_contiguous():
+                    raise ValueError(f"pack_chroma_symbols: qtc_u / qtc_v must be contiguous int16 [{nb}, 64] "
+                                     f"on {self.device}")
+        cap = self.pack_chroma_bound(coding) if out is None else out.shape[1]
+        offs = torch.empty((n, nb + 1), dtype=torch.int32, device=self.device) if offs is None else offs
+        out = torch.empty((n, cap), dtype=torch.uint8, device=self.device) if out is None else out
+        if offs.shape != (n, nb + 1) or offs.dtype != torch.int32 or out.shape[0] != n or out.dtype != torch.uint8:
+            raise ValueError("pack_chroma_symbols: offs must be int32 [n, nb + 1] and out uint8 [n, cap]")
+        if totals is not None and (totals.dtype != torch.int32 or totals.numel() != n or not totals.is_contiguous()):
+            raise ValueError("pack_chroma_symbols: totals must be a contiguous int32 [n]")
+
+        def arr(ts):
+            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        name = "so_pack_chroma_frames_bits" if bits else "so_pack_chroma_frames"
+        rc = getattr(self.lib, name)(n, arr([c.qtc_u for c in csyms]), arr([c.qtc_v for c in csyms]), nb,
+                                     arr(list(offs)), arr(list(out)), int(cap), _lib.ptr(totals),
+                                     _lib.stream_handle(self.device))
+        _lib.check(rc, name)
+        return offs, out
+
+    def unpack_chroma_symbols(self, packed: list, offs: list, coding: str = "varint") -> list:
+        """so_unpack_chroma_frames (coding "varint") or so_unpack_chroma_frames_bits ("bits"):
+        packed chroma streams (device uint8) + their record offsets (device int32 [nb + 1]) ->
+        [(qtc_u, qtc_v)], int16 [nb, 64] each.  Raises ValueError on a malformed stream
+        (synchronises once)."""
+        name = "so_unpack_chroma_frames_bits" if pack_coding_is_bits(coding) else "so_unpack_chroma_frames"
+        n = len(packed)
+        if n == 0 or len(offs) != n:
+            raise ValueError("unpack_chroma_symbols: one offsets tensor per packed stream, at least one")
+        for o in offs:
+            if o.dtype != torch.int32 or o.numel() != self.nb + 1 or not o.is_contiguous():
+                raise ValueError(f"unpack_chroma_symbols: offs must be contiguous int32 [{self.nb + 1}]")
+        q = torch.empty((n, 2, self.nb, 64), dtype=torch.int16, device=self.device)
+        err = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+        def arr(ts):
+            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        rc = getattr(self.lib, name)(n, arr(packed), arr(offs), self.nb, arr([q[i, 0] for i in range(n)]),
+                                     arr([q[i, 1] for i in range(n)]), err.data_ptr(),
+                                     _lib.stream_handle(self.device))
+        _lib.check(rc, name)
+        bad = int(err.item())
+        if bad:
+            raise ValueError(f"{name}: malformed packed chroma stream at record {bad - 1}")
+        return [(q[i, 0], q[i, 1]) for i in range(n)]
+
     # ---- metrics ---------------------------------------------------------------------------
     def sum_rows(self, rows: list, out: torch.Tensor | None = None) -> torch.Tensor:
         """int64 [n]: the sum of each int32 tensor in `rows` (equal lengths), one launch."""

@@ -1,15 +1,28 @@
 """A binary container for the packed symbol stream (so_pack_frames) -- the compact counterpart of
 the reference's two text files (transmit_bitstream, Encoder.py:1544-1573; decode_bitstream,
-decoder.py:686-709).
+decoder.py:686-709).  Little endian.  The version word is layout << 16 | coding: coding 1 is the
+varint coding of the streams (so_pack_frames, so_pack_chroma_frames), coding 2 the "bits" coding
+(so_pack_frames_bits, so_pack_chroma_frames_bits).
+
+Layout 0 (version 1 or 2): luma only, no per-block QP maps.
 
     header   b"SOPK" | u32 version | u32 H | u32 W | u32 bs | u32 nframes | u32 nb
     frame    u8 frame_type | u16 nqp | i8 qp[nqp] (per-row QPs under rate control, else 0)
              | u32 nbytes | u16 block_bytes[nb] | bytes[nbytes]
 
-Little endian.  Version 1 holds the varint coding of the stream (so_pack_frames), version 2
-the "bits" coding (so_pack_frames_bits) in the same layout.  block_bytes lets the GPU decoder (so_unpack_frames) start every block in
-parallel: the offsets are their exclusive prefix sums.  Per-block QP maps (ROI / two-pass RC)
-are not carried: such GOPs use the text bitstream.
+Layout 1: what layout 0 cannot carry -- chroma 4:2:0 and the per-block QP maps of ROI / two-pass
+rate control.
+
+    header   b"SOPK" | u32 (1 << 16 | coding) | u32 H | u32 W | u32 bs | u32 nframes | u32 nb
+             | u32 flags (bit 0: chroma, bit 1: QP maps; any other bit set is rejected)
+             | i32 chroma_qp_offset
+    frame    the layout-0 frame record
+             | if flags & 2:  u8 has_map | u8 qp_map[nb] when has_map     (absolute per-block QPs)
+             | if flags & 1:  u32 cbytes | u16 cblock_bytes[nb] | bytes[cbytes]
+
+block_bytes (cblock_bytes) lets the GPU decoder (so_unpack_frames, so_unpack_chroma_frames) start
+every block (chroma record) in parallel: the offsets are their exclusive prefix sums.  write()
+picks layout 0 whenever it can, so a luma-only GOP without QP maps gives the file it always gave.
 """
 from __future__ import annotations
 
@@ -19,29 +32,55 @@ import numpy as np
 import torch
 
 MAGIC = b"SOPK"
-VERSIONS = {"varint": 1, "bits": 2}              # the stream's coding -> container version
+VERSIONS = {"varint": 1, "bits": 2}              # the stream's coding -> the version word's low half
+FLAG_CHROMA, FLAG_QP_MAPS = 1, 2
 
 
-def write(path: str, eng, symbols: list, qp_rows: list | None = None, coding: str = "varint") -> int:
-    """Pack `symbols` (FrameSymbols on the device) in `coding` ("varint" or "bits") and write
-    the container; returns its size."""
+def _section(offs_h, out, i: int) -> bytes:
+    """u32 nbytes | u16 lengths[nb] | bytes of frame i of a packed stream."""
+    nbytes = int(offs_h[i, -1])
+    lens = np.diff(offs_h[i]).astype(np.uint16)
+    return struct.pack("<I", nbytes) + lens.tobytes() + out[i, :nbytes].cpu().numpy().tobytes()
+
+
+def write(path: str, eng, symbols: list, qp_rows: list | None = None, coding: str = "varint",
+          chroma_symbols: list | None = None) -> int:
+    """Pack `symbols` (FrameSymbols on the device) in `coding` ("varint" or "bits") and write the
+    container; returns its size.  chroma_symbols: the frames' ChromaSymbols, packed in the same
+    coding (layout 1).  Per-block QP maps (s.extra["qp_map"]) are written too (layout 1)."""
     if coding not in VERSIONS:
         raise ValueError(f"packed stream coding {coding!r} (\"varint\" or \"bits\")")
-    if any(s.extra.get("qp_map") is not None for s in symbols):
-        raise NotImplementedError("per-block QP maps (ROI / two-pass RC) are not carried by the packed container")
+    if chroma_symbols is not None and len(chroma_symbols) != len(symbols):
+        raise ValueError(f"{len(chroma_symbols)} chroma frames against {len(symbols)} luma frames")
+    maps = [s.extra.get("qp_map") for s in symbols]
+    maps_h = [None if m is None else m.cpu().numpy().astype(np.int64).reshape(-1) for m in maps]
+    for i, m in enumerate(maps_h):
+        if m is not None and (m.size != eng.nb or int(m.min()) < 0 or int(m.max()) > 255):
+            raise ValueError(f"frame {i}: the QP map must hold {eng.nb} QPs in 0..255")
+    flags = (FLAG_CHROMA if chroma_symbols is not None else 0) | (FLAG_QP_MAPS if any(m is not None for m in maps_h) else 0)
     offs, out = eng.pack_symbols(symbols, coding=coding)
     offs_h = offs.cpu().numpy().astype(np.int64)
+    if flags & FLAG_CHROMA:
+        coffs, cout = eng.pack_chroma_symbols(chroma_symbols, coding=coding)
+        coffs_h = coffs.cpu().numpy().astype(np.int64)
+        qp_offset = int(chroma_symbols[0].qp_offset) if chroma_symbols else 0
     size = 0
     with open(path, "wb") as f:
-        hdr = MAGIC + struct.pack("<6I", VERSIONS[coding], eng.h, eng.w, eng.bs, len(symbols), eng.nb)
+        hdr = MAGIC + struct.pack("<6I", (1 << 16 if flags else 0) | VERSIONS[coding], eng.h, eng.w, eng.bs,
+                                  len(symbols), eng.nb)
+        if flags:
+            hdr += struct.pack("<Ii", flags, qp_offset if flags & FLAG_CHROMA else 0)
         f.write(hdr)
         size += len(hdr)
         for i, s in enumerate(symbols):
             q = list(qp_rows[i]) if qp_rows and qp_rows[i] else []
-            nbytes = int(offs_h[i, -1])
-            lens = np.diff(offs_h[i]).astype(np.uint16)
             rec = (struct.pack("<BH", int(s.frame_type), len(q)) + np.asarray(q, np.int8).tobytes()
-                   + struct.pack("<I", nbytes) + lens.tobytes() + out[i, :nbytes].cpu().numpy().tobytes())
+                   + _section(offs_h, out, i))
+            if flags & FLAG_QP_MAPS:
+                m = maps_h[i]
+                rec += b"\0" if m is None else b"\1" + m.astype(np.uint8).tobytes()
+            if flags & FLAG_CHROMA:
+                rec += _section(coffs_h, cout, i)
             f.write(rec)
             size += len(rec)
     return size
@@ -49,22 +88,29 @@ def write(path: str, eng, symbols: list, qp_rows: list | None = None, coding: st
 
 def read(path: str, device) -> dict:
     """-> {"h", "w", "bs", "nb", "coding", "frame_types", "qp_rows", "packed": [device uint8],
-    "offs": [device int32 [nb + 1]]}; "coding" is "varint" (version 1) or "bits" (version 2)."""
+    "offs": [device int32 [nb + 1]], "layout", "qp_maps", "chroma_packed", "chroma_offs",
+    "chroma_qp_offset"}.  "coding" is "varint" or "bits".  In layout 1: "qp_maps" holds per frame
+    a device int32 [nb] or None (None itself when the file carries no maps), "chroma_packed" /
+    "chroma_offs" the chroma streams like "packed" / "offs" (None without chroma); in layout 0
+    all four are None."""
     with open(path, "rb") as f:
         data = f.read()
     if data[:4] != MAGIC:
         raise ValueError(f"{path}: not a packed StreamOptima bitstream")
     version, h, w, bs, nframes, nb = struct.unpack_from("<6I", data, 4)
-    coding = {v: c for c, v in VERSIONS.items()}.get(version)
-    if coding is None:
+    layout = version >> 16
+    coding = {v: c for c, v in VERSIONS.items()}.get(version & 0xFFFF)
+    if coding is None or layout > 1:
         raise ValueError(f"{path}: container version {version}")
     p = 4 + 24
-    fts, qps, packed, offs = [], [], [], []
-    for _ in range(nframes):
-        ft, nqp = struct.unpack_from("<BH", data, p)
-        p += 3
-        qps.append(np.frombuffer(data, np.int8, nqp, p).astype(int).tolist())
-        p += nqp
+    flags, qp_offset = 0, None
+    if layout == 1:
+        flags, qp_offset = struct.unpack_from("<Ii", data, p)
+        p += 8
+        if flags & ~(FLAG_CHROMA | FLAG_QP_MAPS):
+            raise ValueError(f"{path}: unknown container flags {flags:#x}")
+
+    def section(p: int, what: str):
         (nbytes,) = struct.unpack_from("<I", data, p)
         p += 4
         lens = np.frombuffer(data, np.uint16, nb, p).astype(np.int64)
@@ -72,11 +118,43 @@ def read(path: str, device) -> dict:
         o = np.zeros(nb + 1, np.int64)
         np.cumsum(lens, out=o[1:])
         if o[-1] != nbytes:
-            raise ValueError(f"{path}: block lengths do not add up to the frame's byte count")
-        fts.append(int(ft))
-        offs.append(torch.from_numpy(o.astype(np.int32)).to(device))
-        packed.append(torch.frombuffer(bytearray(data[p:p + nbytes]), dtype=torch.uint8).to(device))
-        p += nbytes
+            raise ValueError(f"{path}: {what} lengths do not add up to the frame's byte count")
+        if p + nbytes > len(data):
+            raise ValueError(f"{path}: the file ends inside a frame")
+        return (p + nbytes, torch.from_numpy(o.astype(np.int32)).to(device),
+                torch.frombuffer(bytearray(data[p:p + nbytes]), dtype=torch.uint8).to(device) if nbytes
+                else torch.zeros(0, dtype=torch.uint8, device=device))
+
+    fts, qps, packed, offs, maps, cpacked, coffs = [], [], [], [], [], [], []
+    try:
+        for _ in range(nframes):
+            ft, nqp = struct.unpack_from("<BH", data, p)
+            p += 3
+            qps.append(np.frombuffer(data, np.int8, nqp, p).astype(int).tolist())
+            p += nqp
+            p, o, b = section(p, "block")
+            fts.append(int(ft))
+            offs.append(o)
+            packed.append(b)
+            if flags & FLAG_QP_MAPS:
+                has = data[p]
+                p += 1
+                if has > 1:
+                    raise ValueError(f"{path}: QP map marker {has}")
+                maps.append(torch.from_numpy(np.frombuffer(data, np.uint8, nb, p).astype(np.int32)).to(device)
+                            if has else None)
+                p += nb if has else 0
+            if flags & FLAG_CHROMA:
+                p, o, b = section(p, "chroma record")
+                coffs.append(o)
+                cpacked.append(b)
+    except (struct.error, IndexError):
+        raise ValueError(f"{path}: the file ends inside a frame") from None
     if p != len(data):
         raise ValueError(f"{path}: {len(data) - p} bytes after the last frame")
-    return {"h": h, "w": w, "bs": bs, "nb": nb, "coding": coding, "frame_types": fts, "qp_rows": qps, "packed": packed, "offs": offs}
+    return {"h": h, "w": w, "bs": bs, "nb": nb, "coding": coding, "frame_types": fts, "qp_rows": qps, "packed": packed,
+            "offs": offs, "layout": layout,
+            "qp_maps": maps if flags & FLAG_QP_MAPS else None,
+            "chroma_packed": cpacked if flags & FLAG_CHROMA else None,
+            "chroma_offs": coffs if flags & FLAG_CHROMA else None,
+            "chroma_qp_offset": qp_offset if flags & FLAG_CHROMA else None}
