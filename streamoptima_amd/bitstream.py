@@ -238,6 +238,67 @@ def varints(buf) -> np.ndarray:
     return (z >> 1) ^ -(z & 1)
 
 
+def _token_list(order, nn: int, token, coefs, what: str) -> np.ndarray:
+    """One (sub-)block's token list read through token() / coefs(n) -> its nn coefficients,
+    row-major: "-L" and L values, "Z" zeros, "0" the trailing zeros, the end also at nn."""
+    q = np.zeros(nn, dtype=np.int16)
+    k = 0
+    while k < nn:
+        t = token()
+        if t < 0:
+            if -t > nn - k:
+                raise ValueError(f"{what}: a list of {-t} values at position {k} of {nn}")
+            q[order[k:k - t]] = coefs(-t)
+            k -= t
+        elif t == 0:
+            break
+        else:
+            if t > nn - k:
+                raise ValueError(f"{what}: a run of {t} zeros at position {k} of {nn}")
+            k += t
+    return q
+
+
+class _BitReader:
+    """MSB-first reader of the "bits" coding; `stream` names the stream in the error messages."""
+
+    def __init__(self, buf, stream: str):
+        self.data = bytes(np.asarray(buf, dtype=np.uint8).reshape(-1))
+        self.nbits = 8 * len(self.data)
+        self.pos = 0
+        self.stream = stream
+
+    def peek(self, n: int) -> int:
+        """The next n <= 40 bits (zeros past the end)."""
+        by = self.pos >> 3
+        w = int.from_bytes(self.data[by:by + 8].ljust(8, b"\0"), "big")
+        return (w >> (64 - (self.pos & 7) - n)) & ((1 << n) - 1)
+
+    def take(self, n: int) -> int:
+        if self.pos + n > self.nbits:
+            raise ValueError(f"{self.stream} ends inside a code")
+        v = self.peek(n)
+        self.pos += n
+        return v
+
+    def ue(self, k: int = 0) -> int:
+        """se_k: the signed value of an order-k code."""
+        zeros = 17 - self.peek(17).bit_length()       # zeros past the end: caught by take
+        if zeros > 16:
+            raise ValueError(f"a prefix of more than 16 zero bits in the {self.stream}")
+        z = self.take(2 * zeros + 1 + k) - (1 << k)
+        if z > 65535:
+            raise ValueError(f"a value outside int16 in the {self.stream}")
+        return (z >> 1) ^ -(z & 1)
+
+    def pad(self) -> int:
+        """The bits up to the next byte boundary (0 when well-formed)."""
+        return self.take(-self.pos % 8)
+
+    def left(self) -> int:
+        return (self.nbits - self.pos) // 8
+
+
 def unpack_frame(buf, nb: int, bs: int, frame_type: int) -> dict:
     """One frame's packed stream -> {"split", "mv", "qtc"} in the canonical symbol layout
     (mv entries past the first of an unsplit block are 0).  Raises ValueError on malformed
@@ -267,36 +328,24 @@ def unpack_frame(buf, nb: int, bs: int, frame_type: int) -> dict:
     qtc = np.zeros((nb, bs * bs), dtype=np.int16)
     sb = bs // 2
     p = 0
+
+    def take(n: int) -> list:
+        nonlocal p
+        if p + n > len(v):
+            raise IndexError
+        p += n
+        return v[p - n:p]
+
     try:
         for b in range(nb):
-            sp = v[p]
-            p += 1
+            sp = take(1)[0]
             if sp != 0 and not (sp == 1 and bs == 16):
                 raise ValueError(f"block {b}: split {sp}")
             split[b] = sp
             nmv = (4 if sp else 1) * (3 if inter else 1)
-            if p + nmv > len(v):
-                raise IndexError
-            mv[b].reshape(-1)[:nmv] = v[p:p + nmv]
-            p += nmv
+            mv[b].reshape(-1)[:nmv] = take(nmv)
             for n, off in ([(sb, j * sb * sb) for j in range(4)] if sp else [(bs, 0)]):
-                order, k = scan_order(n), 0
-                while k < n * n:
-                    t = v[p]
-                    p += 1
-                    if t < 0:
-                        if -t > n * n - k:
-                            raise ValueError(f"block {b}: a list of {-t} values at position {k} of {n * n}")
-                        if p - t > len(v):
-                            raise IndexError
-                        qtc[b, off + order[k:k - t]] = v[p:p - t]
-                        p, k = p - t, k - t
-                    elif t == 0:
-                        break
-                    else:
-                        if t > n * n - k:
-                            raise ValueError(f"block {b}: a run of {t} zeros at position {k} of {n * n}")
-                        k += t
+                qtc[b, off:off + n * n] = _token_list(scan_order(n), n * n, lambda: take(1)[0], take, f"block {b}")
     except IndexError:
         raise ValueError(f"packed stream ends inside block {b}") from None
     if p != len(v):
@@ -311,89 +360,38 @@ def unpack_frame_bits(buf, nb: int, bs: int, frame_type: int) -> dict:
     ValueError on malformed input, by the rules of so_unpack_frames_bits: a ue prefix of more
     than 16 zero bits, a decoded z > 65535, a code running past the last byte, split = 1 at
     block size 8, the token rules of unpack_frame, a set pad bit, bytes after the last block."""
-    data = bytes(np.asarray(buf, dtype=np.uint8).reshape(-1))
-    nbits = 8 * len(data)
-    pos = 0
-
-    def peek(n: int) -> int:
-        """The next n <= 40 bits (zeros past the end)."""
-        by = pos >> 3
-        w = int.from_bytes(data[by:by + 8].ljust(8, b"\0"), "big")
-        return (w >> (64 - (pos & 7) - n)) & ((1 << n) - 1)
-
-    def take(n: int) -> int:
-        nonlocal pos
-        if pos + n > nbits:
-            raise ValueError("packed stream ends inside a code")
-        v = peek(n)
-        pos += n
-        return v
-
-    def ue(k: int = 0) -> int:
-        zeros = 17 - peek(17).bit_length()       # zeros past the end: caught by take
-        if zeros > 16:
-            raise ValueError("a prefix of more than 16 zero bits in the packed stream")
-        z = take(2 * zeros + 1 + k) - (1 << k)
-        if z > 65535:
-            raise ValueError("a value outside int16 in the packed stream")
-        return (z >> 1) ^ -(z & 1)
-
+    r = _BitReader(buf, "packed stream")
     inter = frame_type == 1
     split = np.zeros(nb, dtype=np.uint8)
     mv = np.zeros((nb, 4, 3) if inter else (nb, 4), dtype=np.int16)
     qtc = np.zeros((nb, bs * bs), dtype=np.int16)
     sb = bs // 2
     for b in range(nb):
-        sp, kk = take(1), take(2)
+        sp, kk = r.take(1), r.take(2)
         if sp and bs != 16:
             raise ValueError(f"block {b}: split at block size {bs}")
         split[b] = sp
         nmv = (4 if sp else 1) * (3 if inter else 1)
-        mv[b].reshape(-1)[:nmv] = [ue() for _ in range(nmv)]
+        mv[b].reshape(-1)[:nmv] = [r.ue() for _ in range(nmv)]
+        coefs = lambda n: [r.ue(kk) for _ in range(n)]   # noqa: E731
         for n, off in ([(sb, j * sb * sb) for j in range(4)] if sp else [(bs, 0)]):
-            order, k = scan_order(n), 0
-            while k < n * n:
-                t = ue()
-                if t < 0:
-                    if -t > n * n - k:
-                        raise ValueError(f"block {b}: a list of {-t} values at position {k} of {n * n}")
-                    qtc[b, off + order[k:k - t]] = [ue(kk) for _ in range(-t)]
-                    k -= t
-                elif t == 0:
-                    break
-                else:
-                    if t > n * n - k:
-                        raise ValueError(f"block {b}: a run of {t} zeros at position {k} of {n * n}")
-                    k += t
-        if take(-pos % 8):
+            qtc[b, off:off + n * n] = _token_list(scan_order(n), n * n, r.ue, coefs, f"block {b}")
+        if r.pad():
             raise ValueError(f"block {b}: a set bit in the padding")
-    if pos != nbits:
-        raise ValueError(f"{(nbits - pos) // 8} bytes after the last block")
+    if r.left():
+        raise ValueError(f"{r.left()} bytes after the last block")
     return {"split": split, "mv": mv, "qtc": qtc}
 
 
 # ---- packed chroma stream (so_pack_chroma_frames / so_pack_chroma_frames_bits) -------------------
-def _chroma_lists(nb: int, token, coef, end_of_record) -> dict:
-    """nb records of two 8x8 token lists (U's, then V's) read through token() / coef();
-    end_of_record(b) runs after V's list."""
+def _chroma_lists(nb: int, token, coefs, start_of_record, end_of_record) -> dict:
+    """nb records of two 8x8 token lists (U's, then V's) read through token() / coefs(n);
+    start_of_record() runs before U's list, end_of_record(b) after V's."""
     q = np.zeros((2, nb, 64), dtype=np.int16)
-    order = scan_order(8)
     for b in range(nb):
+        start_of_record()
         for j in range(2):
-            k = 0
-            while k < 64:
-                t = token()
-                if t < 0:
-                    if -t > 64 - k:
-                        raise ValueError(f"record {b}: a list of {-t} values at position {k} of 64")
-                    q[j, b, order[k:k - t]] = [coef() for _ in range(-t)]
-                    k -= t
-                elif t == 0:
-                    break
-                else:
-                    if t > 64 - k:
-                        raise ValueError(f"record {b}: a run of {t} zeros at position {k} of 64")
-                    k += t
+            q[j, b] = _token_list(scan_order(8), 64, token, coefs, f"record {b}")
         end_of_record(b)
     return {"qtc_u": q[0], "qtc_v": q[1]}
 
@@ -418,7 +416,7 @@ def unpack_chroma_frame(buf, nb: int) -> dict:
         p += 1
         return v[p - 1]
 
-    out = _chroma_lists(nb, nxt, nxt, lambda b: None)
+    out = _chroma_lists(nb, nxt, lambda n: [nxt() for _ in range(n)], lambda: None, lambda b: None)
     if p != len(v):
         raise ValueError(f"{len(v) - p} values after the last record")
     return out
@@ -431,51 +429,20 @@ def unpack_chroma_frame_bits(buf, nb: int) -> dict:
     the rules of so_unpack_chroma_frames_bits: a ue prefix of more than 16 zero bits, a decoded
     z > 65535, a code running past the last byte, the token rules of unpack_chroma_frame, a set
     pad bit, bytes after the last record."""
-    data = bytes(np.asarray(buf, dtype=np.uint8).reshape(-1))
-    nbits = 8 * len(data)
-    pos = 0
+    r = _BitReader(buf, "packed chroma stream")
     kk = 0
 
-    def peek(n: int) -> int:
-        by = pos >> 3
-        w = int.from_bytes(data[by:by + 8].ljust(8, b"\0"), "big")
-        return (w >> (64 - (pos & 7) - n)) & ((1 << n) - 1)
-
-    def take(n: int) -> int:
-        nonlocal pos
-        if pos + n > nbits:
-            raise ValueError("packed chroma stream ends inside a code")
-        v = peek(n)
-        pos += n
-        return v
-
-    def ue(k: int = 0) -> int:
-        zeros = 17 - peek(17).bit_length()       # zeros past the end: caught by take
-        if zeros > 16:
-            raise ValueError("a prefix of more than 16 zero bits in the packed chroma stream")
-        z = take(2 * zeros + 1 + k) - (1 << k)
-        if z > 65535:
-            raise ValueError("a value outside int16 in the packed chroma stream")
-        return (z >> 1) ^ -(z & 1)
-
-    def token() -> int:
-        return ue()
-
-    def coef() -> int:
-        return ue(kk)
+    def start_of_record() -> None:
+        nonlocal kk
+        kk = r.take(2)
 
     def end_of_record(b: int) -> None:
-        nonlocal kk
-        if take(-pos % 8):
+        if r.pad():
             raise ValueError(f"record {b}: a set bit in the padding")
-        if b + 1 < nb:
-            kk = take(2)
 
-    if nb > 0:
-        kk = take(2)
-    out = _chroma_lists(nb, token, coef, end_of_record)
-    if pos != nbits:
-        raise ValueError(f"{(nbits - pos) // 8} bytes after the last record")
+    out = _chroma_lists(nb, r.ue, lambda n: [r.ue(kk) for _ in range(n)], start_of_record, end_of_record)
+    if r.left():
+        raise ValueError(f"{r.left()} bytes after the last record")
     return out
 
 

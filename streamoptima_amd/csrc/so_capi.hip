@@ -13,6 +13,7 @@
 
 #include "so_chroma.h"
 #include "so_common.h"
+#include "so_packfmt.h"
 #include "so_run.h"
 
 namespace so {
@@ -50,47 +51,6 @@ int p_tile_launch(const uint8_t* cur, const RefSet& refs, int H, int W, int by0,
                   int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae, uint8_t* out_recon,
                   int32_t* out_sse, hipStream_t st, bool tokens_only = false, const int16_t* prev_mv = nullptr);
 
-struct PackFrame {
-    const uint8_t* split;
-    const int16_t* mv;
-    const int16_t* qtc;
-    uint32_t* offs;
-    uint8_t* out;
-    int frame_type;
-};
-size_t pack_block_bound(int bs);
-struct UnpackFrame {
-    const uint8_t* in;
-    const uint32_t* offs;
-    uint8_t* split;
-    int16_t* mv;
-    int16_t* qtc;
-    int frame_type;
-};
-int unpack_frames_launch(const UnpackFrame* frames, int nframes, int nb, int bs, int32_t* err, hipStream_t st);
-int pack_frames_launch(const PackFrame* frames, int nframes, int nb, int bs, unsigned long long cap, uint32_t* totals,
-                       hipStream_t st);
-size_t pack_bits_block_bound(int bs);   // so_packbits.hip
-int unpack_bits_frames_launch(const UnpackFrame* frames, int nframes, int nb, int bs, int32_t* err, hipStream_t st);
-int pack_bits_frames_launch(const PackFrame* frames, int nframes, int nb, int bs, unsigned long long cap,
-                            uint32_t* totals, hipStream_t st);
-struct ChromaPackFrame {   // so_packchroma.hip
-    const int16_t* qu;
-    const int16_t* qv;
-    uint32_t* offs;
-    uint8_t* out;
-};
-struct ChromaUnpackFrame {
-    const uint8_t* in;
-    const uint32_t* offs;
-    int16_t* qu;
-    int16_t* qv;
-};
-size_t pack_chroma_record_bound(bool bits);
-int pack_chroma_frames_launch(const ChromaPackFrame* frames, int nframes, int nb, bool bits, unsigned long long cap,
-                              uint32_t* totals, hipStream_t st);
-int unpack_chroma_frames_launch(const ChromaUnpackFrame* frames, int nframes, int nb, bool bits, int32_t* err,
-                                hipStream_t st);
 int stripe_halo_push_launch(const uint8_t* plane, int W, int by0, int by1, uint8_t* up, uint8_t* dn,
                             uint32_t* up_flags, uint32_t* dn_flags, int gf, uint32_t epoch, hipStream_t st);
 int frame_push_launch(const uint8_t* plane, int H, int W, uint8_t* dst, uint32_t* flags, uint32_t epoch,

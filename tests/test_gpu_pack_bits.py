@@ -212,6 +212,24 @@ def test_pack_bits_capacity_guard_edges(gpu):
         _check_pack(offs, out, tot, [blk], cap)
 
 
+def test_pack_bits_on_a_second_device(gpu):
+    """As test_gpu_pack_edges.py test_pack_unpack_on_a_second_device, in the bits coding: 33 blocks
+    of m16, two inter frames, packed and unpacked on cuda:0 and then with cuda:1 current and every
+    buffer on it, each time the model's bytes and the corpus back."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("fewer than two devices are visible")
+    nb, n = 33, packbitcases.corpus("m16", 1)[0].size
+    frames, blocks = zip(*[_frame("m16", 1, (i * 37 + np.arange(nb)) % n) for i in range(2)])
+    cap = _cap_for(blocks)
+    for dev in (gpu, torch.device("cuda:1")):
+        with torch.cuda.device(dev):
+            offs, out, tot = _pack(dev, list(frames), 16, cap)
+            _check_pack(offs, out, tot, blocks, cap)
+            u = _Unpack(dev, [b"".join(blk) for blk in blocks], [_offsets(blk) for blk in blocks], nb, 16)
+            u.launch([0, 1], [1, 1])
+            _check_unpack(u.fetch(), frames)
+
+
 # ---- damaged and non-canonical input: the unpacker against the strict model -------------------------
 def _mutated_frames(kind, ftype):
     """[(stream, offs, {block: the model's verdict on its bytes})]: a valid frame of short corpus

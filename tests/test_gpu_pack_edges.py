@@ -203,6 +203,26 @@ def test_pack_capacity_guard_edges(gpu):
         _check_pack(offs, out, tot, [blk], cap)
 
 
+def test_pack_unpack_on_a_second_device(gpu):
+    """The scan tables belong to the code object, so they are there on every device of a process:
+    33 blocks of m16, two inter frames, packed and unpacked first on cuda:0 and then, in the same
+    process, with cuda:1 current and every buffer on it -- each time the writer's bytes and the
+    corpus back.  (Tables filled once per process would be zero on the second device: wrong
+    bytes, every index still in bounds.)"""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("fewer than two devices are visible")
+    nb, n = 33, packcases.corpus("m16", 1)[0].size
+    frames, blocks = zip(*[_frame("m16", 1, (i * 37 + np.arange(nb)) % n) for i in range(2)])
+    cap = _cap_for(blocks)
+    for dev in (gpu, torch.device("cuda:1")):
+        with torch.cuda.device(dev):
+            offs, out, tot = _pack(dev, list(frames), 16, cap)
+            _check_pack(offs, out, tot, blocks, cap)
+            u = _Unpack(dev, [b"".join(blk) for blk in blocks], [_offsets(blk) for blk in blocks], nb, 16)
+            u.launch([0, 1], [1, 1])
+            _check_unpack(u.fetch(), frames)
+
+
 # ---- the unpacker against the Python writer's bytes ------------------------------------------------
 @pytest.mark.parametrize("nframes", NFRAMES)
 @pytest.mark.parametrize("kind", packcases.KINDS)

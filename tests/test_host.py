@@ -219,3 +219,82 @@ def test_run_kernel_selection_truth_table(tmp_path):
                    check=True, capture_output=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
+
+
+def _unpack_check_cases():
+    """[(coding 0/1, kind 0 luma 16 / 1 luma 8 / 2 chroma, frame type, bytes, the strict model's verdict:
+    None = malformed, else (split, mv, qtc) flat)]: the corpora of tests/packcases.py, tests/packbitcases.py
+    and tests/packchromaref.py and every mutant of theirs."""
+    import packbitcases
+    import packcases
+    import packchromaref
+    from packbitsref import unpack_block_bits_strict
+    from packref import unpack_block_strict
+    cases = []
+
+    def luma(coding, bs, ftype, data, model):
+        v = model(data, bs, ftype)
+        want = None if v is None else (int(v["split"]), np.asarray(v["mv"]).reshape(-1), np.asarray(v["qtc"]))
+        cases.append((coding, 0 if bs == 16 else 1, ftype, data, want))
+
+    for kind in packcases.KINDS:
+        bs = packcases.block_size(kind)
+        for ftype in (0, 1):
+            for data in packcases.block_bytes(kind, ftype):
+                luma(0, bs, ftype, data, unpack_block_strict)
+            for data in packbitcases.block_bytes(kind, ftype):
+                luma(1, bs, ftype, data, unpack_block_bits_strict)
+            base = packcases.mutation_base(kind, ftype)
+            for b, block in enumerate(base):
+                for _, data in packcases.mutations(block, bs, ftype, prev_byte=base[b - 1][-1]):
+                    luma(0, bs, ftype, data, unpack_block_strict)
+            for block in packbitcases.mutant_base(kind, ftype):
+                for _, data in packbitcases.mutants(block, bs, ftype):
+                    luma(1, bs, ftype, data, unpack_block_bits_strict)
+    for c, coding in enumerate(packchromaref.CODINGS):
+        todo = [(d, packchromaref.unpack_record_strict(d, coding)) for d in packchromaref.record_bytes(coding)]
+        todo += [(d, v) for _, d, v in packchromaref.mutants(coding)]
+        for data, v in todo:
+            want = None if isinstance(v, str) else (0, np.zeros(0, np.int16), np.concatenate([v["qtc_u"], v["qtc_v"]]))
+            cases.append((c, 2, 0, data, want))
+    return cases
+
+
+def test_unpack_record_bodies_under_sanitizers(tmp_path):
+    """The strict decoders of streamoptima_amd/csrc/so_packfmt.h (the record bodies the unpack kernels
+    run), compiled for the host with AddressSanitizer and UndefinedBehaviorSanitizer
+    (tests/host/unpack_check.cpp: a child process, every record and every output in a heap allocation
+    of exactly its size): on every corpus record and every mutant, in both codings, accept / reject
+    and the decoded split, mv values and coefficients equal the strict models', and no access leaves
+    a record's bytes or its outputs."""
+    import shutil
+    import struct
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx is not None, "no host C++ compiler"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "unpack_check")
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-isystem", "/opt/rocm/include",
+                    os.path.join(root, "tests", "host", "unpack_check.cpp"), "-o", exe],
+                   check=True, capture_output=True)
+    cases = _unpack_check_cases()
+    assert sum(c[4] is None for c in cases) > 1000 and sum(c[4] is not None for c in cases) > 1000
+    assert {(c[0], c[1]) for c in cases} == {(a, b) for a in (0, 1) for b in (0, 1, 2)}
+    src, dst = str(tmp_path / "records.bin"), str(tmp_path / "decoded.bin")
+    with open(src, "wb") as f:
+        for coding, kind, ftype, data, _ in cases:
+            f.write(struct.pack("<BBBBI", coding, kind, ftype, 0, len(data)) + data)
+    r = subprocess.run([exe, src, dst], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    rec = np.dtype([("bad", np.uint8), ("split", np.uint8), ("mv", np.int16, 12), ("q", np.int16, 256)])
+    got = np.fromfile(dst, dtype=rec)
+    assert got.size == len(cases)
+    for i, (coding, kind, ftype, data, want) in enumerate(cases):
+        g = got[i]
+        assert bool(g["bad"]) == (want is None), (i, coding, kind, ftype, data.hex())
+        if want is not None:
+            split, mv, q = want
+            assert g["split"] == split, (i, coding, kind, ftype, data.hex())
+            assert np.array_equal(g["mv"][:mv.size], mv) and not g["mv"][mv.size:].any(), (i, coding, kind, ftype)
+            assert np.array_equal(g["q"][:q.size], q) and not g["q"][q.size:].any(), (i, coding, kind, ftype)
