@@ -784,6 +784,16 @@ int so_unpack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t
  *   (exclusive offsets with the total in offs[i][nb]; a record that would pass `cap` is not
  *   written; totals, which may be NULL, stored at system scope).  A NULL required pointer or
  *   nb <= 0 is SO_E_INVALID; nframes = 0 is SO_OK.  Stream-ordered, no host synchronisation.
+ * so_pack_chroma_frames_after / _bits_after: the same records placed behind bytes that are already
+ *   in out[i] (a frame's luma stream), so that one buffer holds the frame's whole payload.
+ *   base[i] points at one device uint32 -- typically the luma stream's offs[i] + nb, written by
+ *   so_pack_frames_ex earlier on the same stream; it is read on the device by the write pass and
+ *   never on the host.  Record b of frame i goes to out[i] + *base[i] + offs[i][b]; offs stays
+ *   relative (the exclusive scan of the chroma record lengths, the chroma total in offs[i][nb]),
+ *   so the unpackers and a container's chroma lengths read it unchanged.  A record is written
+ *   only if *base[i] + offs[i][b+1] <= cap.  totals[i] = *base[i] + offs[i][nb] (may be NULL;
+ *   stored at system scope).  Bytes before *base[i] and after the written records are not
+ *   touched.  A NULL base or base[i] is SO_E_INVALID, as for the other required pointers.
  * so_unpack_chroma_frames / _bits: the inverse, as so_unpack_frames: every record decoded from
  *   exactly its bytes [offs[b], offs[b+1]) into the zeroed blocks; malformed input sets the
  *   device int32 *err to 1 + a bad record's index (zero it first); a bad record's outputs are
@@ -798,6 +808,14 @@ int so_pack_chroma_frames_bits(int nframes, const int16_t* const* qtc_u,
                                const int16_t* const* qtc_v, int nb, uint32_t* const* offs,
                                uint8_t* const* out, unsigned long long cap, uint32_t* totals,
                                void* stream);
+int so_pack_chroma_frames_after(int nframes, const int16_t* const* qtc_u,
+                                const int16_t* const* qtc_v, int nb, uint32_t* const* offs,
+                                uint8_t* const* out, const uint32_t* const* base,
+                                unsigned long long cap, uint32_t* totals, void* stream);
+int so_pack_chroma_frames_bits_after(int nframes, const int16_t* const* qtc_u,
+                                     const int16_t* const* qtc_v, int nb, uint32_t* const* offs,
+                                     uint8_t* const* out, const uint32_t* const* base,
+                                     unsigned long long cap, uint32_t* totals, void* stream);
 int so_unpack_chroma_frames(int nframes, const uint8_t* const* packed, const uint32_t* const* offs,
                             int nb, int16_t* const* qtc_u, int16_t* const* qtc_v, int32_t* err,
                             void* stream);

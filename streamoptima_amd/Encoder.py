@@ -301,32 +301,48 @@ class Y_Video_codec(BlockAPI):
             planes.copy_(src)
         return planes
 
-    def _encode_chroma_gop(self, eng, uv_dev, syms) -> dict:
-        """U and V of every frame of a GOP from its luma symbols: a stream-ordered chain of one
-        launch per frame behind the luma work (a P-frame's chroma reads the chroma reconstruction
-        of its references).  The reference list is the luma one's: one all-128 plane at first, an
-        I-frame clears it, every reconstruction is appended, the oldest dropped at nRefFrames."""
-        n = len(syms)
+    def _check_uv(self, eng, uv_dev, n: int) -> None:
         if uv_dev is None or tuple(uv_dev.shape) != (n, 2, eng.h // 2, eng.w // 2) or uv_dev.dtype != torch.uint8:
             raise ValueError(f"chroma=True needs uv planes [{n}, 2, {eng.h // 2}, {eng.w // 2}] uint8 on the device")
+
+    def _chroma_frames(self, eng, uv_dev, out: list, pre: list | None = None):
+        """-> step(k, sym): enqueue frame k's U and V from its luma symbols, append the ChromaSymbols
+        to `out` (into pre[k] when given) and keep the chroma reference list.  The list is the luma
+        one's: one all-128 plane at first, an I-frame clears it, every reconstruction is appended,
+        the oldest dropped at nRefFrames.  Frames must come in order (a P-frame's chroma reads the
+        chroma reconstruction of its references): a stream-ordered chain of one launch per frame."""
         if getattr(eng, "_cref128", None) is None:
             eng._cref128 = alloc_planes(1, eng.h // 2, eng.w // 2, self.device, fill=128)[0]
         refs_u, refs_v = [eng._cref128], [eng._cref128]
-        out = []
-        for i, s in enumerate(syms):
-            if s.frame_type == 0:
-                refs_u, refs_v = [], []
-            c = eng.encode_chroma(s, uv_dev[i, 0], uv_dev[i, 1], refs_u, refs_v, self.chroma_qp_offset)
+
+        def step(k: int, sym) -> None:
+            if sym.frame_type == 0:
+                refs_u.clear()
+                refs_v.clear()
+            c = eng.encode_chroma(sym, uv_dev[k, 0], uv_dev[k, 1], refs_u, refs_v, self.chroma_qp_offset,
+                                  out=pre[k] if pre is not None else None)
             out.append(c)
-            if i < n - 1:
-                if len(refs_u) >= self.nRefFrames:
-                    refs_u.pop(0)
-                    refs_v.pop(0)
-                refs_u.append(c.recon_u)
-                refs_v.append(c.recon_v)
+            if len(refs_u) >= self.nRefFrames:
+                refs_u.pop(0)
+                refs_v.pop(0)
+            refs_u.append(c.recon_u)
+            refs_v.append(c.recon_v)
+        return step
+
+    @staticmethod
+    def _chroma_result(eng, csyms: list) -> dict:
         # per frame: SSE of U, SSE of V, tokens of U, tokens of V -- one reduction per GOP
-        sums = eng.sum_rows([r for c in out for r in (c.sse[0], c.sse[1], c.tokens[0], c.tokens[1])]).view(n, 4)
-        return {"chroma_symbols": out, "chroma_sums": sums}
+        sums = eng.sum_rows([r for c in csyms for r in (c.sse[0], c.sse[1], c.tokens[0], c.tokens[1])])
+        return {"chroma_symbols": csyms, "chroma_sums": sums.view(len(csyms), 4)}
+
+    def _encode_chroma_gop(self, eng, uv_dev, syms, pre: list | None = None) -> dict:
+        """U and V of every frame of a GOP behind the GOP's luma work (_chroma_frames)."""
+        self._check_uv(eng, uv_dev, len(syms))
+        out = []
+        step = self._chroma_frames(eng, uv_dev, out, pre)
+        for i, s in enumerate(syms):
+            step(i, s)
+        return self._chroma_result(eng, out)
 
     def _rc_on(self):
         return self.RCFlag is not None and self.RCFlag > 0
@@ -445,7 +461,8 @@ class Y_Video_codec(BlockAPI):
         return psnr_per_frame
 
     def encode_device(self, frames_dev: torch.Tensor, intra_dur: int, symbols=None, check: bool = True,
-                      chunk: int | None = None, wait_input=None, on_output=None, uv_dev: torch.Tensor | None = None):
+                      chunk: int | None = None, wait_input=None, on_output=None, uv_dev: torch.Tensor | None = None,
+                      chroma_symbols: list | None = None):
         """The GOP loop on device-resident frames [F, Hp, Wp].  Returns symbols per frame and
         a device SSE array.  check=True ends with one host read of the persistent runs'
         timeout count (Engine.check_run: raises if a dependency wait timed out); a caller
@@ -462,14 +479,31 @@ class Y_Video_codec(BlockAPI):
         With chroma=True, uv_dev holds the frames' chroma planes [F, 2, Hp/2, Wp/2] (uint8, padded
         with 128) and the result also holds "chroma_symbols" (a ChromaSymbols per frame) and
         "chroma_sums" (device int64 [F, 4]: SSE of U, SSE of V, tokens of U, tokens of V), enqueued
-        after the GOP's luma work with no host synchronisation.  Luma is untouched by it."""
-        if self.chroma and (wait_input is not None or on_output is not None or chunk is not None):
-            raise NotImplementedError("chroma in the streaming encoder is not built")
+        after the GOP's luma work with no host synchronisation.  Luma is untouched by it.  Given
+        any streaming hook, the chroma frames of a unit [k0, k1) are instead enqueued right after
+        that unit's luma work (wait_input(k0, k1) covers their planes too) and handed on as
+        on_output(k0, k1, syms, csyms); the symbols are the same.  chroma_symbols: a preallocated
+        ChromaSymbols per frame to write into (Engine.new_chroma_symbols), like `symbols`."""
         wait_input_default, on_output_default = wait_input is None, on_output is None
+        stream_chroma = self.chroma and not (wait_input_default and on_output_default and chunk is None)
         wait_input = wait_input or (lambda k0, k1: None)
-        on_output = on_output or (lambda k0, k1, syms: None)
+        on_output = on_output or (lambda *unit: None)
         eng = self.engine()
         nframes = frames_dev.shape[0]
+        if chroma_symbols is not None and (not self.chroma or len(chroma_symbols) != nframes):
+            raise ValueError(f"chroma_symbols needs chroma=True and one ChromaSymbols for each of the {nframes} frames")
+        out_csyms = []
+        if stream_chroma:
+            self._check_uv(eng, uv_dev, nframes)
+            chroma_step = self._chroma_frames(eng, uv_dev, out_csyms, chroma_symbols)
+
+        def emit(k0, k1, unit):
+            """a unit's luma work is enqueued: its chroma behind it, then the caller's hook"""
+            if not stream_chroma:
+                return on_output(k0, k1, unit)
+            for k, s in zip(range(k0, k1), unit):
+                chroma_step(k, s)
+            return on_output(k0, k1, unit, out_csyms[k0:k1])
         # the reference's initial reference list: one all-128 frame (Encoder.py:1798), never
         # written, so one plane per engine serves every GOP (no fill per call)
         if getattr(eng, "_ref128", None) is None:
@@ -527,7 +561,8 @@ class Y_Video_codec(BlockAPI):
         if pipelined and chunk is None and intra_dur < nframes - 1 and wait_input_default and on_output_default:
             # several P-runs between I-frames: independent chains, interleaved in one launch
             return self.encode_gops_device([frames_dev], intra_dur, symbols=[symbols] if symbols else None,
-                                           check=check, uv_gops=[uv_dev] if self.chroma else None)[0]
+                                           check=check, uv_gops=[uv_dev] if self.chroma else None,
+                                           chroma_symbols=[chroma_symbols] if chroma_symbols else None)[0]
         i = 0
         while i < nframes:
             if (pipelined or pipelined2) and i % intra_dur != 0:
@@ -557,7 +592,7 @@ class Y_Video_codec(BlockAPI):
                     self.set_Qp(qp_sched[-1])
                 ref_frames = [outs[-1].recon]
                 ref_float = [False]
-                on_output(i, j, outs)
+                emit(i, j, outs)
                 i = j
                 continue
             wait_input(i, i + 1)
@@ -582,7 +617,7 @@ class Y_Video_codec(BlockAPI):
             out_syms.append(sym)
             ftypes.append(sym.frame_type)
             qp_rows.append(list(qp_sched) if rc_on else [])
-            on_output(i, i + 1, [sym])
+            emit(i, i + 1, [sym])
             if i < nframes - 1:
                 if len(ref_frames) >= self.nRefFrames:
                     ref_frames.pop(0)
@@ -597,8 +632,10 @@ class Y_Video_codec(BlockAPI):
         res = {"symbols": out_syms, "sse": sse, "frame_type": ftypes, "qp_rows": qp_rows}
         if self.ssim:
             res["ssim"] = self._ssim_device(eng, frames_dev, out_syms)
-        if self.chroma:
-            res.update(self._encode_chroma_gop(eng, uv_dev, out_syms))
+        if stream_chroma:
+            res.update(self._chroma_result(eng, out_csyms))
+        elif self.chroma:
+            res.update(self._encode_chroma_gop(eng, uv_dev, out_syms, chroma_symbols))
         return res
 
     def _ssim_device(self, eng, frames_dev, syms) -> torch.Tensor:
@@ -607,7 +644,7 @@ class Y_Video_codec(BlockAPI):
                         self.w_pixels)
 
     def encode_gops_device(self, gops: list, intra_dur: int, symbols=None, check: bool = True,
-                           uv_gops: list | None = None) -> list:
+                           uv_gops: list | None = None, chroma_symbols: list | None = None) -> list:
         """Several GOPs (device-resident [F, Hp, Wp] each, e.g. consecutive GOPs of one stream
         or GOPs of different streams) encoded together: every I-frame first (they depend on
         nothing), then the P-frame runs of ALL the GOPs interleaved in one persistent launch
@@ -618,7 +655,8 @@ class Y_Video_codec(BlockAPI):
         once per GOP).  Covers the persistent-run configuration (no two-pass RC / ROI / RCFlag>1
         P->I switch, nRefFrames 1); returns one encode_device-style dict per GOP.
         symbols: optional per-GOP lists of preallocated FrameSymbols to reuse.
-        uv_gops (chroma=True): per GOP the chroma planes [F, 2, Hp/2, Wp/2], as encode_device."""
+        uv_gops (chroma=True): per GOP the chroma planes [F, 2, Hp/2, Wp/2], as encode_device;
+        chroma_symbols: optional per-GOP lists of preallocated ChromaSymbols to reuse."""
         eng = self.engine()
         if self.chroma and (uv_gops is None or len(uv_gops) != len(gops)):
             raise ValueError("chroma=True needs uv_gops, one [F, 2, Hp/2, Wp/2] tensor per GOP")
@@ -657,7 +695,8 @@ class Y_Video_codec(BlockAPI):
             if self.ssim:
                 res[-1]["ssim"] = self._ssim_device(eng, frames_dev, syms)
             if self.chroma:
-                res[-1].update(self._encode_chroma_gop(eng, uv_gops[g], syms))
+                res[-1].update(self._encode_chroma_gop(eng, uv_gops[g], syms,
+                                                       chroma_symbols[g] if chroma_symbols else None))
         if check:
             eng.check_run()
         return res

@@ -94,6 +94,8 @@ _SIGS = {
     "so_pack_chroma_bits_bound": ([_i], _sz),
     "so_pack_chroma_frames": ([_i, _vp, _vp, _i, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
     "so_pack_chroma_frames_bits": ([_i, _vp, _vp, _i, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
+    "so_pack_chroma_frames_after": ([_i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
+    "so_pack_chroma_frames_bits_after": ([_i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
     "so_unpack_chroma_frames": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "so_unpack_chroma_frames_bits": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "so_fme_plane_stride": ([_i, _i], _sz),

@@ -1388,19 +1388,22 @@ size_t so_pack_chroma_bits_bound(int nb) { return nb <= 0 ? 0 : (size_t)nb * pac
 
 static int pack_chroma_any(const char* fn, bool bits, int nframes, const int16_t* const* qtc_u,
                            const int16_t* const* qtc_v, int nb, uint32_t* const* offs, uint8_t* const* out,
-                           unsigned long long cap, uint32_t* totals, void* stream) {
+                           bool after, const uint32_t* const* base, unsigned long long cap, uint32_t* totals,
+                           void* stream) {
     if (nb <= 0 || nframes < 0) {
         set_error("%s: nb %d / nframes %d", fn, nb, nframes);
         return SO_E_INVALID;
     }
     if (nframes == 0) return SO_OK;
     SO_NEED(qtc_u, fn); SO_NEED(qtc_v, fn); SO_NEED(offs, fn); SO_NEED(out, fn);
+    if (after) SO_NEED(base, fn);
     std::vector<ChromaPackFrame> fr((size_t)nframes);
     for (int i = 0; i < nframes; ++i) {
         SO_NEED(qtc_u[i], fn); SO_NEED(qtc_v[i], fn); SO_NEED(offs[i], fn); SO_NEED(out[i], fn);
-        fr[i] = ChromaPackFrame{qtc_u[i], qtc_v[i], offs[i], out[i]};
+        if (after) SO_NEED(base[i], fn);
+        fr[i] = ChromaPackFrame{qtc_u[i], qtc_v[i], offs[i], out[i], after ? base[i] : nullptr};
     }
-    return pack_chroma_frames_launch(fr.data(), nframes, nb, bits, cap, totals, (hipStream_t)stream);
+    return pack_chroma_frames_launch(fr.data(), nframes, nb, bits, after, cap, totals, (hipStream_t)stream);
 }
 
 static int unpack_chroma_any(const char* fn, bool bits, int nframes, const uint8_t* const* packed,
@@ -1423,14 +1426,29 @@ static int unpack_chroma_any(const char* fn, bool bits, int nframes, const uint8
 int so_pack_chroma_frames(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
                           uint32_t* const* offs, uint8_t* const* out, unsigned long long cap, uint32_t* totals,
                           void* stream) {
-    return pack_chroma_any("so_pack_chroma_frames", false, nframes, qtc_u, qtc_v, nb, offs, out, cap, totals, stream);
+    return pack_chroma_any("so_pack_chroma_frames", false, nframes, qtc_u, qtc_v, nb, offs, out, false, nullptr, cap,
+                           totals, stream);
 }
 
 int so_pack_chroma_frames_bits(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
                                uint32_t* const* offs, uint8_t* const* out, unsigned long long cap, uint32_t* totals,
                                void* stream) {
-    return pack_chroma_any("so_pack_chroma_frames_bits", true, nframes, qtc_u, qtc_v, nb, offs, out, cap, totals,
-                           stream);
+    return pack_chroma_any("so_pack_chroma_frames_bits", true, nframes, qtc_u, qtc_v, nb, offs, out, false, nullptr,
+                           cap, totals, stream);
+}
+
+int so_pack_chroma_frames_after(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
+                                uint32_t* const* offs, uint8_t* const* out, const uint32_t* const* base,
+                                unsigned long long cap, uint32_t* totals, void* stream) {
+    return pack_chroma_any("so_pack_chroma_frames_after", false, nframes, qtc_u, qtc_v, nb, offs, out, true, base, cap,
+                           totals, stream);
+}
+
+int so_pack_chroma_frames_bits_after(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
+                                     uint32_t* const* offs, uint8_t* const* out, const uint32_t* const* base,
+                                     unsigned long long cap, uint32_t* totals, void* stream) {
+    return pack_chroma_any("so_pack_chroma_frames_bits_after", true, nframes, qtc_u, qtc_v, nb, offs, out, true, base,
+                           cap, totals, stream);
 }
 
 int so_unpack_chroma_frames(int nframes, const uint8_t* const* packed, const uint32_t* const* offs, int nb,

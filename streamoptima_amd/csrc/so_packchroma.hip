@@ -12,6 +12,12 @@
 // Passes as so_pack.hip: per-record byte counts (one wave per record), pack_scan_kernel (reused
 // unchanged) for the offsets and the per-frame totals, then the bytes.  Same capacity guard: a
 // record whose end offset passes `cap` is not written.
+//
+// so_pack_chroma_frames_after / _bits_after: the same passes with the write pass alone knowing a
+// per-frame base, *f.base, a device word that earlier work on the stream wrote (the luma scan's
+// offs[nb]): record b lands at out + base + offs[b], guarded by base + offs[b + 1] <= cap, and the
+// write pass, not the scan, stores totals[i] = base + offs[nb].  offs stays relative.  A record may
+// thus start at any byte: both store paths write single bytes (out[i] = stage[i], stage_store).
 #include "so_packfmt.h"
 
 namespace so {
@@ -21,6 +27,13 @@ namespace so {
 struct ChromaIn {
     uint32_t q;
     uint32_t o0, o1;  // offs[b], offs[b + 1] (write pass)
+};
+
+// The write pass's view of a frame: `out` already moved to the frame's base, `cap` lowered by it
+// (0 when the base alone passes it: no record of one byte or more fits).
+struct ChromaDst {
+    uint8_t* out;
+    unsigned long long cap;
 };
 
 template <bool WRITE>
@@ -46,7 +59,7 @@ SO_DEV PackRuns<2> chroma_runs(const ChromaIn& in, int lane, int16_t* __restrict
 
 // ---- varint coding -------------------------------------------------------------------------------
 template <bool WRITE>
-SO_DEV void pack_chroma_one(const ChromaPackFrame& f, int b, unsigned long long cap, int lane, const ChromaIn& in,
+SO_DEV void pack_chroma_one(const ChromaPackFrame& f, int b, const ChromaDst& d, int lane, const ChromaIn& in,
                             int16_t* __restrict__ sq, uint8_t* __restrict__ stage, const int* idx) {
     const PackRuns<2> r = chroma_runs(in, lane, sq, idx);
     int total;
@@ -55,18 +68,18 @@ SO_DEV void pack_chroma_one(const ChromaPackFrame& f, int b, unsigned long long 
         if (lane == 0) f.offs[b] = (uint32_t)total;
         return;
     }
-    if (in.o1 > cap) return;
+    if (in.o1 > d.cap) return;
     // bytes into the wave's LDS stage, then out with consecutive lanes on consecutive bytes
     put_varints(stage + ex, r);
     __builtin_amdgcn_wave_barrier();
-    uint8_t* out = f.out + in.o0;
+    uint8_t* out = d.out + in.o0;
     for (int i = lane; i < total; i += 64) out[i] = stage[i];
 }
 
 // ---- bits coding ---------------------------------------------------------------------------------
 // The order k is picked over both lists (so_packfmt.h pick_order); it is the record's first two bits.
 template <bool WRITE>
-SO_DEV void pack_chroma_bits_one(const ChromaPackFrame& f, int b, unsigned long long cap, int lane,
+SO_DEV void pack_chroma_bits_one(const ChromaPackFrame& f, int b, const ChromaDst& d, int lane,
                                  const ChromaIn& in, int16_t* __restrict__ sq, uint32_t* __restrict__ stage,
                                  const int* idx) {
     const PackRuns<2> r = chroma_runs(in, lane, sq, idx);
@@ -85,25 +98,38 @@ SO_DEV void pack_chroma_bits_one(const ChromaPackFrame& f, int b, unsigned long 
         if (lane == 0) f.offs[b] = (uint32_t)nbytes;
         return;
     }
-    if (in.o1 > cap) return;
+    if (in.o1 > d.cap) return;
     stage_zero(stage, nbytes, lane);
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) stage_or<kChromaStageWords>(stage, 0, (uint32_t)k << 30);
     const int pos = 2 + (mex >> 10) + order_bits(mex & 0x3FF, cex, k);
     put_codes<kChromaStageWords>(stage, pos, r, l, k);
     __builtin_amdgcn_wave_barrier();
-    stage_store(f.out + in.o0, stage, nbytes, lane);
+    stage_store(d.out + in.o0, stage, nbytes, lane);
 }
 
 // Each wave packs records b = wave, wave + nwaves, ... of its frame (blockIdx.y), the next
-// record's inputs loaded before the current one is packed (so_packfmt.h pack_loop).
-template <bool WRITE, bool BITS>
-__global__ void __launch_bounds__(256) pack_chroma_kernel(const ChromaPackArgs a, int nb, unsigned long long cap) {
+// record's inputs loaded before the current one is packed (so_packfmt.h pack_loop).  AFTER (the
+// write pass of the _after entries): the frame's base is read once (one uniform load; a null
+// pointer is base 0) and, given `totals`, the frame's first thread stores base + offs[nb] there at
+// system scope.  The plain entries' instantiations know no base, leave the totals to the scan and
+// pass null.
+template <bool WRITE, bool BITS, bool AFTER = false>
+__global__ void __launch_bounds__(256) pack_chroma_kernel(const ChromaPackArgs a, int nb, unsigned long long cap,
+                                                          uint32_t* totals) {
     __shared__ alignas(4) int16_t sq[4][128];
     __shared__ uint32_t stage[WRITE ? 4 : 1][WRITE ? (BITS ? kChromaStageWords : kChromaBound / 4 + 2) : 1];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int w0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wv), nw = gridDim.x * 4;
     const ChromaPackFrame f = a.f[blockIdx.y];   // a copy: its pointers stay in SGPRs
+    ChromaDst d{f.out, cap};
+    if constexpr (WRITE && AFTER) {
+        const uint32_t base = f.base ? *f.base : 0u;
+        d.out += base;
+        d.cap = cap > base ? cap - base : 0ull;
+        if (totals && blockIdx.x == 0 && threadIdx.x == 0)
+            __hip_atomic_store(totals + blockIdx.y, base + f.offs[nb], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     // this lane's two scan positions as int16 indices into the staged record (U at 0, V at 64)
     int idx[2];
 #pragma unroll
@@ -115,9 +141,9 @@ __global__ void __launch_bounds__(256) pack_chroma_kernel(const ChromaPackArgs a
         w0, nw, nb, [&](int b) { return chroma_load<WRITE>(f, b, nb, lane); },
         [&](int b, const ChromaIn& in) {
             if constexpr (BITS)
-                pack_chroma_bits_one<WRITE>(f, b, cap, lane, in, sq[wv], stage[WRITE ? wv : 0], idx);
+                pack_chroma_bits_one<WRITE>(f, b, d, lane, in, sq[wv], stage[WRITE ? wv : 0], idx);
             else   // the varint stage is bytes: character accesses alias anything
-                pack_chroma_one<WRITE>(f, b, cap, lane, in, sq[wv], reinterpret_cast<uint8_t*>(stage[WRITE ? wv : 0]),
+                pack_chroma_one<WRITE>(f, b, d, lane, in, sq[wv], reinterpret_cast<uint8_t*>(stage[WRITE ? wv : 0]),
                                        idx);
         });
 }
@@ -141,18 +167,28 @@ __global__ void __launch_bounds__(256) unpack_chroma_kernel(const ChromaUnpackAr
     if (r.bad) __hip_atomic_store(err, b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-int pack_chroma_frames_launch(const ChromaPackFrame* frames, int nframes, int nb, bool bits, unsigned long long cap,
-                              uint32_t* totals, hipStream_t st) {
+// after: the frames carry a base; the totals then come from the write pass (base + offs[nb]), not
+// from the scan
+int pack_chroma_frames_launch(const ChromaPackFrame* frames, int nframes, int nb, bool bits, bool after,
+                              unsigned long long cap, uint32_t* totals, hipStream_t st) {
     return for_frame_chunks<ChromaPackArgs>(
         frames, nframes, "pack chroma kernels", [&](const ChromaPackArgs& a, int n, int f0) {
             PackArgs sa{};   // the scan reads only `offs`
             for (int i = 0; i < n; ++i) sa.f[i].offs = a.f[i].offs;
             const dim3 grid = pack_grid(nb, n);
-            if (bits) hipLaunchKernelGGL((pack_chroma_kernel<false, true>), grid, dim3(256), 0, st, a, nb, cap);
-            else hipLaunchKernelGGL((pack_chroma_kernel<false, false>), grid, dim3(256), 0, st, a, nb, cap);
-            pack_scan_launch(sa, n, nb, totals ? totals + f0 : nullptr, st);
-            if (bits) hipLaunchKernelGGL((pack_chroma_kernel<true, true>), grid, dim3(256), 0, st, a, nb, cap);
-            else hipLaunchKernelGGL((pack_chroma_kernel<true, false>), grid, dim3(256), 0, st, a, nb, cap);
+            uint32_t* const tot = totals ? totals + f0 : nullptr;
+            uint32_t* const none = nullptr;
+            if (bits) hipLaunchKernelGGL((pack_chroma_kernel<false, true>), grid, dim3(256), 0, st, a, nb, cap, none);
+            else hipLaunchKernelGGL((pack_chroma_kernel<false, false>), grid, dim3(256), 0, st, a, nb, cap, none);
+            pack_scan_launch(sa, n, nb, after ? none : tot, st);
+            if (!after) {
+                if (bits) hipLaunchKernelGGL((pack_chroma_kernel<true, true>), grid, dim3(256), 0, st, a, nb, cap, none);
+                else hipLaunchKernelGGL((pack_chroma_kernel<true, false>), grid, dim3(256), 0, st, a, nb, cap, none);
+            } else if (bits) {
+                hipLaunchKernelGGL((pack_chroma_kernel<true, true, true>), grid, dim3(256), 0, st, a, nb, cap, tot);
+            } else {
+                hipLaunchKernelGGL((pack_chroma_kernel<true, false, true>), grid, dim3(256), 0, st, a, nb, cap, tot);
+            }
         });
 }
 

@@ -43,6 +43,7 @@ struct ChromaPackFrame {
     const int16_t* qv;
     uint32_t* offs;        // [nb + 1] exclusive offsets (pass 1 writes counts)
     uint8_t* out;
+    const uint32_t* base;  // device word: the records go to out + *base + offs[b]; null: 0
 };
 struct ChromaUnpackFrame {
     const uint8_t* in;
@@ -92,8 +93,8 @@ int pack_bits_frames_launch(const PackFrame* frames, int nframes, int nb, int bs
                             uint32_t* totals, hipStream_t st);
 int unpack_bits_frames_launch(const UnpackFrame* frames, int nframes, int nb, int bs, int32_t* err, hipStream_t st);
 // so_packchroma.hip
-int pack_chroma_frames_launch(const ChromaPackFrame* frames, int nframes, int nb, bool bits, unsigned long long cap,
-                              uint32_t* totals, hipStream_t st);
+int pack_chroma_frames_launch(const ChromaPackFrame* frames, int nframes, int nb, bool bits, bool after,
+                              unsigned long long cap, uint32_t* totals, hipStream_t st);
 int unpack_chroma_frames_launch(const ChromaUnpackFrame* frames, int nframes, int nb, bool bits, int32_t* err,
                                 hipStream_t st);
 

@@ -673,12 +673,20 @@ class Engine:
         return int(bound(self.nb))
 
     def pack_chroma_symbols(self, csyms: list, offs: torch.Tensor | None = None, out: torch.Tensor | None = None,
-                            totals: torch.Tensor | None = None, coding: str = "varint"):
+                            totals: torch.Tensor | None = None, coding: str = "varint",
+                            after: torch.Tensor | None = None, totals_ptr: int | None = None):
         """Each frame's chroma coefficients (ChromaSymbols.qtc_u / .qtc_v) as one packed byte stream
         on the device (include/streamoptima.h so_pack_chroma_frames); asynchronous.  Returns (offs
         int32 [n, nb + 1], out uint8 [n, cap]) as pack_symbols does: frame i's stream is
         out[i, :offs[i, nb]], record b starts at offs[i, b].  The default capacity never overflows.
-        totals: a device int32 [n] that also receives offs[i, nb].  coding: "varint" or "bits"."""
+        totals: a device int32 [n] that also receives offs[i, nb]; totals_ptr: instead of it, a
+        device address of n uint32 (hostmem.device_ptr of a page-locked host array).  coding:
+        "varint" or "bits".
+        after: the int32 [n, nb + 1] offsets pack_symbols filled for the same frames, earlier on this
+        stream (so_pack_chroma_frames_after).  `out` is then required and is the tensor pack_symbols
+        wrote, with room for both streams: frame i's chroma records go behind its luma bytes, to
+        out[i, after[i, nb] + offs[i, b]], offs staying relative, and the totals receive the
+        combined length after[i, nb] + offs[i, nb]."""
         bits = pack_coding_is_bits(coding)
         n, nb = len(csyms), self.nb
         if n == 0:
@@ -688,19 +696,38 @@ class Engine:
                 if t.dtype != torch.int16 or t.numel() != nb * 64 or t.device != self.device or not t.is_contiguous():
                     raise ValueError(f"pack_chroma_symbols: qtc_u / qtc_v must be contiguous int16 [{nb}, 64] "
                                      f"on {self.device}")
+        if after is not None:
+            if (after.dtype != torch.int32 or tuple(after.shape) != (n, nb + 1) or after.device != self.device
+                    or after.stride(1) != 1):
+                raise ValueError(f"pack_chroma_symbols: after must be the int32 [{n}, {nb + 1}] offsets of "
+                                 f"pack_symbols on {self.device}, rows contiguous")
+            need = self.pack_bound(nb, coding) + self.pack_chroma_bound(coding)
+            if out is None or out.dim() != 2 or out.shape[1] < need:
+                raise ValueError(f"pack_chroma_symbols: with after, out must be pack_symbols' out with a row "
+                                 f"capacity of at least {need} bytes")
         cap = self.pack_chroma_bound(coding) if out is None else out.shape[1]
         offs = torch.empty((n, nb + 1), dtype=torch.int32, device=self.device) if offs is None else offs
         out = torch.empty((n, cap), dtype=torch.uint8, device=self.device) if out is None else out
         if offs.shape != (n, nb + 1) or offs.dtype != torch.int32 or out.shape[0] != n or out.dtype != torch.uint8:
             raise ValueError("pack_chroma_symbols: offs must be int32 [n, nb + 1] and out uint8 [n, cap]")
+        if after is not None and (offs.device != self.device or out.device != self.device or offs.stride(1) != 1
+                                  or out.stride(1) != 1):
+            raise ValueError(f"pack_chroma_symbols: offs and out must be on {self.device} with contiguous rows")
         if totals is not None and (totals.dtype != torch.int32 or totals.numel() != n or not totals.is_contiguous()):
             raise ValueError("pack_chroma_symbols: totals must be a contiguous int32 [n]")
+        if totals is not None and totals_ptr is not None:
+            raise ValueError("pack_chroma_symbols: totals or totals_ptr, not both")
+        tot = _lib.ptr(totals) if totals_ptr is None else int(totals_ptr)
 
         def arr(ts):
             return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
         name = "so_pack_chroma_frames_bits" if bits else "so_pack_chroma_frames"
+        base = ()
+        if after is not None:
+            name += "_after"
+            base = (arr([after[i, nb:] for i in range(n)]),)
         rc = getattr(self.lib, name)(n, arr([c.qtc_u for c in csyms]), arr([c.qtc_v for c in csyms]), nb,
-                                     arr(list(offs)), arr(list(out)), int(cap), _lib.ptr(totals),
+                                     arr(list(offs)), arr(list(out)), *base, int(cap), tot,
                                      _lib.stream_handle(self.device))
         _lib.check(rc, name)
         return offs, out

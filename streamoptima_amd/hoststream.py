@@ -24,6 +24,7 @@ from __future__ import annotations
 
 import time
 
+import numpy as np
 import torch
 
 from .engine import alloc_planes
@@ -34,14 +35,35 @@ from .hwqueue import dedicated_stream
 class _Buffers:
     """One GOP in flight: device frames, packed streams and their pinned host copies."""
 
-    def __init__(self, eng, nframes: int, dev):
-        self.frames_dev = alloc_planes(nframes, eng.h, eng.w, dev)
-        self.offs = torch.empty((nframes, eng.nb + 1), dtype=torch.int32, device=dev)
-        self.packed = torch.empty((nframes, eng.pack_bound()), dtype=torch.uint8, device=dev)
-        self.tot_h = pinned_empty((nframes,), torch.int32)
-        self.tot_dptr = device_ptr(self.tot_h)     # the pack's scan stores each frame's length here
+    def __init__(self, eng, nframes: int, dev, chroma: bool = False, lengths: bool = False):
+        nb, F = eng.nb, nframes
+        self.frames_dev = alloc_planes(F, eng.h, eng.w, dev)
+        self.offs = torch.empty((F, nb + 1), dtype=torch.int32, device=dev)
+        cap = eng.pack_bound() + (eng.pack_chroma_bound() if chroma else 0)   # a row: luma, then chroma
+        self.packed = torch.empty((F, cap), dtype=torch.uint8, device=dev)
         self.packed_h = pinned_empty(tuple(self.packed.shape))
-        self.sse_h = pinned_empty((nframes,), torch.int64)
+        # the small host arrays in one page-locked slab (an allocation there is 2 MB at least):
+        # int64 sse [F] | int64 chroma sums [F, 4] | int32 luma lengths [F] | int32 combined lengths [F]
+        slab = pinned_empty((F * (8 + 32 + 4 + 4),))
+        self.sse_h = slab[:8 * F].view(torch.int64)
+        self.csum_h = slab[8 * F:40 * F].view(torch.int64).view(F, 4)
+        self.tot_h = slab[40 * F:44 * F].view(torch.int32)
+        self.all_h = slab[44 * F:48 * F].view(torch.int32)
+        # the packs' last passes store each frame's length here: luma's into tot_h
+        # (so_pack_frames_ex), luma + chroma into all_h (so_pack_chroma_frames_after)
+        self.tot_dptr = device_ptr(slab) + 40 * F
+        self.all_dptr = device_ptr(slab) + 44 * F
+        self.len_h = self.all_h if chroma else self.tot_h     # what a frame's download copies
+        if chroma:
+            self.uv_dev = alloc_planes(F * 2, eng.h // 2, eng.w // 2, dev).view(F, 2, eng.h // 2, eng.w // 2)
+            self.coffs = torch.empty((F, nb + 1), dtype=torch.int32, device=dev)
+        if lengths:
+            # per-block byte counts: diff(offs) on the compute stream (a block is at most 1201 bytes,
+            # a chroma record 600), row 0 luma, row 1 chroma, and their host copy
+            k = 2 if chroma else 1
+            self.diff32 = torch.empty((k, F, nb), dtype=torch.int32, device=dev)
+            self.blen = torch.empty((k, F, nb), dtype=torch.int16, device=dev)
+            self.blen_h = pinned_empty((k, F, nb), torch.int16)
         self.enc_done = None      # compute-stream event: this set's frames are no longer read
         self.d2h_done = None      # D2H-stream event: this set's packed streams are downloaded
         self.gop = None           # (index, frame types) of the GOP it holds
@@ -64,9 +86,11 @@ class _PackedViews:
 
 
 class HostStreamEncoder:
-    def __init__(self, codec, nframes: int, chunk: int = 2, nbuf: int = 1, upload: str = "chunk"):
+    def __init__(self, codec, nframes: int, chunk: int = 2, nbuf: int = 1, upload: str = "chunk",
+                 lengths: bool = False):
         """upload: "chunk" = one H2D copy per encode unit (the I-frame, each P-run chunk), "frame"
-        = one per frame."""
+        = one per frame.  lengths: the results also hold each frame's per-block byte counts
+        ("block_bytes", and "chroma_block_bytes" with a chroma=True codec), which write_packed needs."""
         eng = codec.engine()
         self.codec, self.eng, self.nframes, self.chunk = codec, eng, int(nframes), int(chunk)
         if upload not in ("chunk", "frame"):
@@ -79,7 +103,12 @@ class HostStreamEncoder:
         self.d2h = dedicated_stream(self.dev, "hoststream.d2h")
         self.comp = dedicated_stream(self.dev, "hoststream.compute")
         self.syms = None
-        self.bufs = [_Buffers(eng, self.nframes, self.dev) for _ in range(max(1, int(nbuf)))]
+        self.chroma, self.lengths = bool(codec.chroma), bool(lengths)
+        # like the luma symbols, one set of ChromaSymbols serves every buffer set: the compute
+        # stream packs a GOP's symbols before the next GOP's work overwrites them
+        self.csyms = [eng.new_chroma_symbols() for _ in range(self.nframes)] if self.chroma else None
+        self.bufs = [_Buffers(eng, self.nframes, self.dev, self.chroma, self.lengths)
+                     for _ in range(max(1, int(nbuf)))]
 
     @property
     def frames_dev(self):
@@ -88,6 +117,21 @@ class HostStreamEncoder:
     def _check(self, frames_host):
         if tuple(frames_host.shape) != tuple(self.bufs[0].frames_dev.shape) or not frames_host.is_pinned():
             raise ValueError("frames_host must be pinned uint8 of the encoder's padded frame shape")
+
+    def _check_uv(self, uv_gops, ngops: int) -> list:
+        """One pinned uint8 [F, 2, Hp/2, Wp/2] per GOP with a chroma=True codec, none otherwise."""
+        if not self.chroma:
+            if uv_gops is not None:
+                raise ValueError("uv planes were given, but the codec was built with chroma=False")
+            return [None] * ngops
+        shape = tuple(self.bufs[0].uv_dev.shape)
+        if uv_gops is None or len(uv_gops) != ngops:
+            raise ValueError(f"a chroma=True codec needs uv planes: one pinned uint8 {list(shape)} tensor per GOP")
+        for uv in uv_gops:
+            if (not isinstance(uv, torch.Tensor) or uv.dtype != torch.uint8 or tuple(uv.shape) != shape
+                    or not uv.is_contiguous() or not uv.is_pinned()):
+                raise ValueError(f"uv planes must be pinned contiguous uint8 {list(shape)} (padded with 128)")
+        return list(uv_gops)
 
     def _units(self, intra_dur: int) -> list:
         """The frame ranges encode_device works on in turn: each I-frame, and the P-runs of at
@@ -102,10 +146,11 @@ class HostStreamEncoder:
             i = j
         return r
 
-    def _upload(self, b: _Buffers, frames_host, intra_dur: int) -> list:
+    def _upload(self, b: _Buffers, frames_host, intra_dur: int, uv_host=None) -> list:
         """Queue the GOP's upload; returns per frame the event after the copy that carries it
         (one copy per encode unit: 16.6 MB copies ran at 52.6 GB/s, 8.3 MB ones at 50.0 on the
-        GPU box, tools/s4_links.py)."""
+        GPU box, tools/s4_links.py).  A unit's U and V planes follow its Y planes, inside the
+        same event."""
         up = [None] * self.nframes
         units = self._units(intra_dur) if self.upload == "chunk" else [(i, i + 1) for i in range(self.nframes)]
         with torch.cuda.stream(self.h2d):
@@ -113,37 +158,81 @@ class HostStreamEncoder:
                 self.h2d.wait_event(b.enc_done)      # the GOP that last used these frames is encoded
             for k0, k1 in units:
                 b.frames_dev[k0:k1].copy_(frames_host[k0:k1], non_blocking=True)
+                if uv_host is not None:
+                    b.uv_dev[k0:k1].copy_(uv_host[k0:k1], non_blocking=True)
                 ev = torch.cuda.Event()
                 ev.record(self.h2d)
                 up[k0:k1] = [ev] * (k1 - k0)
         return up
 
     def _result(self, b: _Buffers) -> dict:
-        nbytes = b.tot_h.tolist()
-        return {"packed": _PackedViews(b.packed_h, nbytes), "bytes": nbytes,
-                "sse": b.sse_h.clone(), "frame_type": b.gop[1]}
+        nbytes = b.len_h.tolist()
+        res = {"packed": _PackedViews(b.packed_h, nbytes), "bytes": nbytes,
+               "sse": b.sse_h.clone(), "frame_type": b.gop[1]}
+        if self.chroma:
+            res["luma_bytes"] = b.tot_h.tolist()
+            res["chroma_sse"] = b.csum_h[:, :2].clone()
+            res["chroma_tokens"] = b.csum_h[:, 2:].clone()
+        if self.lengths:
+            lens = b.blen_h.numpy().view(np.uint16)
+            res["block_bytes"] = lens[0]
+            if self.chroma:
+                res["chroma_block_bytes"] = lens[1]
+        return res
 
-    def encode(self, frames_host: torch.Tensor, intra_dur: int) -> dict:
+    def encode(self, frames_host: torch.Tensor, intra_dur: int, uv_host: torch.Tensor | None = None) -> dict:
         """frames_host: pinned uint8 [F, Hp, Wp].  Returns {"packed": [host uint8 view per
         frame], "bytes": [...], "sse": host int64 [F], "frame_type": [...]} once everything
-        is in host memory (the views stay valid until the next call)."""
+        is in host memory (the views stay valid until the next call).
+        With a chroma=True codec, uv_host: pinned uint8 [F, 2, Hp/2, Wp/2], padded with 128
+        (Y_Video_codec._upload_uv_padded's layout); "packed"[i] is then frame i's luma stream
+        followed by its chroma stream, "bytes" the combined length, and the result also holds
+        "luma_bytes" (where to split) and "chroma_sse" / "chroma_tokens", host int64 [F, 2] (U, V).
+        With lengths=True: "block_bytes" and, with chroma, "chroma_block_bytes", host uint16 [F, nb]."""
         out = []
-        self.encode_stream([frames_host], intra_dur, lambda k, r: out.append(r))
+        self.encode_stream([frames_host], intra_dur, lambda k, r: out.append(r),
+                           uv_gops=None if uv_host is None else [uv_host])
         return out[0]
 
-    def encode_stream(self, gops: list, intra_dur: int, consume, trace: list | None = None) -> None:
+    def write_packed(self, path: str, result: dict, qp_rows: list | None = None) -> int:
+        """A result of an encoder built with lengths=True as a packed container
+        (packedfile.write_frames; decoder.decode_packed_file reads it): the file
+        transmit_packed / transmit_packed420 writes for the same GOP.  qp_rows: the frames'
+        per-row QPs under rate control (encode_device's "qp_rows").  Returns the file size."""
+        from . import packedfile
+        if "block_bytes" not in result:
+            raise ValueError("write_packed needs the per-block lengths: build the encoder with lengths=True")
+        if (self.codec.RCFlag is not None and self.codec.RCFlag >= 3) or self.codec.roi_block_offsets() is not None:
+            raise NotImplementedError("write_packed: the stream does not download per-block QP maps (ROI / two-pass RC)")
+        frames = []
+        for i, ft in enumerate(result["frame_type"]):
+            p = result["packed"][i].numpy()
+            f = {"frame_type": ft, "qp_rows": qp_rows[i] if qp_rows else [], "block_bytes": result["block_bytes"][i]}
+            if self.chroma:
+                n = result["luma_bytes"][i]
+                f.update(payload=p[:n], chroma_payload=p[n:], chroma_block_bytes=result["chroma_block_bytes"][i])
+            else:
+                f["payload"] = p
+            frames.append(f)
+        return packedfile.write_frames(path, self.eng.h, self.eng.w, self.eng.bs, self.eng.nb, "varint", frames,
+                                       chroma_qp_offset=self.codec.chroma_qp_offset if self.chroma else None)
+
+    def encode_stream(self, gops: list, intra_dur: int, consume, trace: list | None = None,
+                      uv_gops: list | None = None) -> None:
         """Encode GOPs back to back; consume(k, result) is called for GOP k, in order, once its
         symbols are in host memory and before its buffers are reused (the result's views are
         valid only inside the call).  With two buffer sets (nbuf=2) GOP k+1's upload runs
-        during GOP k's encode."""
+        during GOP k's encode.  uv_gops: with a chroma=True codec, each GOP's chroma planes
+        (encode's uv_host)."""
         for g in gops:
             self._check(g)
+        uv_gops = self._check_uv(uv_gops, len(gops))
         caller = torch.cuda.current_stream(self.dev)
         self.comp.wait_stream(caller)       # the caller's earlier work on the inputs / buffers
         with torch.cuda.stream(self.comp):
-            self._encode_stream(gops, intra_dur, consume, trace)
+            self._encode_stream(gops, intra_dur, consume, trace, uv_gops)
 
-    def _encode_stream(self, gops: list, intra_dur: int, consume, trace) -> None:
+    def _encode_stream(self, gops: list, intra_dur: int, consume, trace, uv_gops) -> None:
         eng, comp, nb = self.eng, self.comp, len(self.bufs)
         if self.syms is None:
             self.syms = [eng.new_symbols(0 if i % intra_dur == 0 else 1) for i in range(self.nframes)]
@@ -158,13 +247,16 @@ class HostStreamEncoder:
         def drain(upto_len):
             while len(pending) > upto_len:
                 b, k0, k1, ev = pending.pop(0)
-                ev.synchronize()                    # byte counts of frames [k0, k1) are in tot_h
+                ev.synchronize()                    # byte counts of frames [k0, k1) are in len_h
                 self.d2h.wait_event(ev)
                 mark(f"d2h_go {k0}", self.d2h)
                 with torch.cuda.stream(self.d2h):
                     for i in range(k0, k1):
-                        n = int(b.tot_h[i])
+                        n = int(b.len_h[i])
                         b.packed_h[i, :n].copy_(b.packed[i, :n], non_blocking=True)
+                    if self.lengths:
+                        for r in range(b.blen.shape[0]):     # contiguous rows: plain async copies
+                            b.blen_h[r, k0:k1].copy_(b.blen[r, k0:k1], non_blocking=True)
                 if k1 == self.nframes:              # the GOP's last chunk: its download is queued
                     b.d2h_done = torch.cuda.Event()
                     b.d2h_done.record(self.d2h)
@@ -187,10 +279,10 @@ class HostStreamEncoder:
             if b.gop is not None:
                 retire(b)                            # GOP k - nb: long finished when nb > 1
             if k == 0 or nb == 1:
-                ups[k] = self._upload(b, g, intra_dur)
+                ups[k] = self._upload(b, g, intra_dur, uv_gops[k])
                 mark(f"up_end {k}", self.h2d)
             if nb > 1 and k + 1 < len(gops):       # the next GOP's upload, queued before this encode
-                ups[k + 1] = self._upload(self.bufs[(k + 1) % nb], gops[k + 1], intra_dur)
+                ups[k + 1] = self._upload(self.bufs[(k + 1) % nb], gops[k + 1], intra_dur, uv_gops[k + 1])
                 mark(f"up_end {k + 1}", self.h2d)
             up = ups.pop(k)
             if b.d2h_done is not None:
@@ -202,9 +294,17 @@ class HostStreamEncoder:
                 comp.wait_event(up[k1 - 1])
                 mark(f"chunk_go {k0}", comp)
 
-            def on_output(k0, k1, syms, b=b):
+            def on_output(k0, k1, syms, csyms=None, b=b):
                 # the scan stores the frames' lengths straight into tot_h (so_pack_frames_ex)
                 eng.pack_symbols(syms, b.offs[k0:k1], b.packed[k0:k1], totals_ptr=b.tot_dptr + 4 * k0)
+                if csyms is not None:
+                    # the chroma records behind each frame's luma bytes, the combined lengths into all_h
+                    eng.pack_chroma_symbols(csyms, b.coffs[k0:k1], b.packed[k0:k1], after=b.offs[k0:k1],
+                                            totals_ptr=b.all_dptr + 4 * k0)
+                if self.lengths:
+                    for r, o in enumerate((b.offs, b.coffs) if csyms is not None else (b.offs,)):
+                        torch.sub(o[k0:k1, 1:], o[k0:k1, :-1], out=b.diff32[r, k0:k1])
+                        b.blen[r, k0:k1].copy_(b.diff32[r, k0:k1])
                 ev = torch.cuda.Event()
                 ev.record(comp)
                 mark(f"chunk_end {k0}", comp)
@@ -212,8 +312,11 @@ class HostStreamEncoder:
                 drain(1)                             # the chunk before this one
 
             res = self.codec.encode_device(b.frames_dev, intra_dur, symbols=self.syms, check=False,
-                                           chunk=self.chunk, wait_input=wait_input, on_output=on_output)
+                                           chunk=self.chunk, wait_input=wait_input, on_output=on_output,
+                                           **({"uv_dev": b.uv_dev, "chroma_symbols": self.csyms} if self.chroma else {}))
             b.sse_h.copy_(res["sse"], non_blocking=True)
+            if self.chroma:
+                b.csum_h.copy_(res["chroma_sums"], non_blocking=True)
             b.enc_done = torch.cuda.Event()
             b.enc_done.record(comp)
             mark(f"enc_end {k}", comp)

@@ -21,8 +21,9 @@ rate control.
              | if flags & 1:  u32 cbytes | u16 cblock_bytes[nb] | bytes[cbytes]
 
 block_bytes (cblock_bytes) lets the GPU decoder (so_unpack_frames, so_unpack_chroma_frames) start
-every block (chroma record) in parallel: the offsets are their exclusive prefix sums.  write()
-picks layout 0 whenever it can, so a luma-only GOP without QP maps gives the file it always gave.
+every block (chroma record) in parallel: the offsets are their exclusive prefix sums.  The
+writer (write_frames: host data in; write packs device symbols and calls it) picks layout 0
+whenever it can, so a luma-only GOP without QP maps gives the file it always gave.
 """
 from __future__ import annotations
 
@@ -36,54 +37,88 @@ VERSIONS = {"varint": 1, "bits": 2}              # the stream's coding -> the ve
 FLAG_CHROMA, FLAG_QP_MAPS = 1, 2
 
 
-def _section(offs_h, out, i: int) -> bytes:
-    """u32 nbytes | u16 lengths[nb] | bytes of frame i of a packed stream."""
-    nbytes = int(offs_h[i, -1])
-    lens = np.diff(offs_h[i]).astype(np.uint16)
-    return struct.pack("<I", nbytes) + lens.tobytes() + out[i, :nbytes].cpu().numpy().tobytes()
+def _section(lens, payload, nb: int, what: str) -> bytes:
+    """u32 nbytes | u16 lengths[nb] | bytes: one frame's luma blocks or chroma records."""
+    lens = np.asarray(lens).reshape(-1)
+    data = payload if isinstance(payload, (bytes, bytearray)) else np.ascontiguousarray(
+        np.asarray(payload, dtype=np.uint8)).tobytes()
+    if lens.size != nb:
+        raise ValueError(f"{what}: {lens.size} lengths for {nb} blocks")
+    if lens.size and (int(lens.min()) < 0 or int(lens.max()) > 0xFFFF):
+        raise ValueError(f"{what}: a length does not fit a u16")
+    if int(lens.astype(np.int64).sum()) != len(data):
+        raise ValueError(f"{what}: the lengths add up to {int(lens.astype(np.int64).sum())}, the payload has "
+                         f"{len(data)} bytes")
+    return struct.pack("<I", len(data)) + lens.astype("<u2").tobytes() + data
+
+
+def write_frames(path: str, h: int, w: int, bs: int, nb: int, coding: str, frames: list,
+                 chroma_qp_offset: int | None = None) -> int:
+    """Write the container from host data; returns its size.  frames: one dict per frame with
+    "frame_type", "qp_rows" (the per-row QPs under rate control, else empty), "block_bytes" ([nb]
+    lengths) and "payload" (the frame's packed luma bytes); optionally "qp_map" ([nb] absolute QPs
+    in 0..255, or None); optionally "chroma_block_bytes" and "chroma_payload", for all frames or
+    for none.  chroma_qp_offset goes into the header of a file with chroma.  Layout 0 when no frame
+    has chroma or a QP map, else layout 1.  This is the one statement of the format's write side."""
+    if coding not in VERSIONS:
+        raise ValueError(f"packed stream coding {coding!r} (\"varint\" or \"bits\")")
+    has_c = ["chroma_payload" in f or "chroma_block_bytes" in f for f in frames]
+    if any(has_c) and not all("chroma_payload" in f and "chroma_block_bytes" in f for f in frames):
+        raise ValueError("chroma_block_bytes and chroma_payload: both, and for every frame or for none")
+    maps_h = []
+    for i, f in enumerate(frames):
+        m = f.get("qp_map")
+        m = None if m is None else np.asarray(m).astype(np.int64).reshape(-1)
+        if m is not None and (m.size != nb or int(m.min()) < 0 or int(m.max()) > 255):
+            raise ValueError(f"frame {i}: the QP map must hold {nb} QPs in 0..255")
+        maps_h.append(m)
+    flags = (FLAG_CHROMA if any(has_c) else 0) | (FLAG_QP_MAPS if any(m is not None for m in maps_h) else 0)
+    hdr = MAGIC + struct.pack("<6I", (1 << 16 if flags else 0) | VERSIONS[coding], h, w, bs, len(frames), nb)
+    if flags:
+        hdr += struct.pack("<Ii", flags, int(chroma_qp_offset or 0) if flags & FLAG_CHROMA else 0)
+    recs = []
+    for i, f in enumerate(frames):
+        q = list(f.get("qp_rows") or [])
+        rec = (struct.pack("<BH", int(f["frame_type"]), len(q)) + np.asarray(q, np.int8).tobytes()
+               + _section(f["block_bytes"], f["payload"], nb, f"frame {i}"))
+        if flags & FLAG_QP_MAPS:
+            m = maps_h[i]
+            rec += b"\0" if m is None else b"\1" + m.astype(np.uint8).tobytes()
+        if flags & FLAG_CHROMA:
+            rec += _section(f["chroma_block_bytes"], f["chroma_payload"], nb, f"frame {i} chroma")
+        recs.append(rec)
+    with open(path, "wb") as fh:        # nothing is written when an input is refused
+        fh.write(hdr)
+        for rec in recs:
+            fh.write(rec)
+    return len(hdr) + sum(len(r) for r in recs)
 
 
 def write(path: str, eng, symbols: list, qp_rows: list | None = None, coding: str = "varint",
           chroma_symbols: list | None = None) -> int:
     """Pack `symbols` (FrameSymbols on the device) in `coding` ("varint" or "bits") and write the
-    container; returns its size.  chroma_symbols: the frames' ChromaSymbols, packed in the same
-    coding (layout 1).  Per-block QP maps (s.extra["qp_map"]) are written too (layout 1)."""
+    container (write_frames); returns its size.  chroma_symbols: the frames' ChromaSymbols, packed
+    in the same coding (layout 1).  Per-block QP maps (s.extra["qp_map"]) are written too (layout 1)."""
     if coding not in VERSIONS:
         raise ValueError(f"packed stream coding {coding!r} (\"varint\" or \"bits\")")
     if chroma_symbols is not None and len(chroma_symbols) != len(symbols):
         raise ValueError(f"{len(chroma_symbols)} chroma frames against {len(symbols)} luma frames")
-    maps = [s.extra.get("qp_map") for s in symbols]
-    maps_h = [None if m is None else m.cpu().numpy().astype(np.int64).reshape(-1) for m in maps]
-    for i, m in enumerate(maps_h):
-        if m is not None and (m.size != eng.nb or int(m.min()) < 0 or int(m.max()) > 255):
-            raise ValueError(f"frame {i}: the QP map must hold {eng.nb} QPs in 0..255")
-    flags = (FLAG_CHROMA if chroma_symbols is not None else 0) | (FLAG_QP_MAPS if any(m is not None for m in maps_h) else 0)
-    offs, out = eng.pack_symbols(symbols, coding=coding)
-    offs_h = offs.cpu().numpy().astype(np.int64)
-    if flags & FLAG_CHROMA:
-        coffs, cout = eng.pack_chroma_symbols(chroma_symbols, coding=coding)
-        coffs_h = coffs.cpu().numpy().astype(np.int64)
-        qp_offset = int(chroma_symbols[0].qp_offset) if chroma_symbols else 0
-    size = 0
-    with open(path, "wb") as f:
-        hdr = MAGIC + struct.pack("<6I", (1 << 16 if flags else 0) | VERSIONS[coding], eng.h, eng.w, eng.bs,
-                                  len(symbols), eng.nb)
-        if flags:
-            hdr += struct.pack("<Ii", flags, qp_offset if flags & FLAG_CHROMA else 0)
-        f.write(hdr)
-        size += len(hdr)
-        for i, s in enumerate(symbols):
-            q = list(qp_rows[i]) if qp_rows and qp_rows[i] else []
-            rec = (struct.pack("<BH", int(s.frame_type), len(q)) + np.asarray(q, np.int8).tobytes()
-                   + _section(offs_h, out, i))
-            if flags & FLAG_QP_MAPS:
-                m = maps_h[i]
-                rec += b"\0" if m is None else b"\1" + m.astype(np.uint8).tobytes()
-            if flags & FLAG_CHROMA:
-                rec += _section(coffs_h, cout, i)
-            f.write(rec)
-            size += len(rec)
-    return size
+
+    def host(offs, out):
+        offs_h = offs.cpu().numpy().astype(np.int64)
+        return [(np.diff(o), out[i, :int(o[-1])].cpu().numpy()) for i, o in enumerate(offs_h)]
+    luma = host(*eng.pack_symbols(symbols, coding=coding))
+    chroma = host(*eng.pack_chroma_symbols(chroma_symbols, coding=coding)) if chroma_symbols else None
+    frames = []
+    for i, s in enumerate(symbols):
+        m = s.extra.get("qp_map")
+        f = {"frame_type": int(s.frame_type), "qp_rows": qp_rows[i] if qp_rows and qp_rows[i] else [],
+             "block_bytes": luma[i][0], "payload": luma[i][1], "qp_map": None if m is None else m.cpu().numpy()}
+        if chroma is not None:
+            f["chroma_block_bytes"], f["chroma_payload"] = chroma[i]
+        frames.append(f)
+    qp_offset = int(chroma_symbols[0].qp_offset) if chroma_symbols else None
+    return write_frames(path, eng.h, eng.w, eng.bs, eng.nb, coding, frames, chroma_qp_offset=qp_offset)
 
 
 def read(path: str, device) -> dict:
