@@ -823,6 +823,74 @@ int so_unpack_chroma_frames_bits(int nframes, const uint8_t* const* packed,
                                  const uint32_t* const* offs, int nb, int16_t* const* qtc_u,
                                  int16_t* const* qtc_v, int32_t* err, void* stream);
 
+/* ---- fused decode: packed records straight to pixels (so_decode.hip) -------------------------
+ * The receiving side's hot path.  Both entry points compute exactly what the unpack entry points
+ * followed by the reconstruction entry points compute, without the dense int16 coefficients in
+ * global memory: a workgroup parses 64 records into LDS and transforms them from there.  All
+ * pointer arrays (packed, offs, qp_row, qp_map, refs0*, split, mv, out_*) are HOST arrays of
+ * device pointers; `coding` is the container's number: 1 varint (so_pack_frames), 2 bits
+ * (so_pack_frames_bits).  One kernel launch per frame, enqueued in order on `stream`: stream order
+ * carries the dependency of a frame on the reconstructions before it.  No host synchronisation.
+ *
+ * so_decode_p_frames: a run of nframes consecutive luma P-frames.  Frame i is decoded from
+ *   packed[i] with the block offsets offs[i][0..nb] (nb = (H / bs) * (W / bs); the formats
+ *   so_unpack_frames / so_unpack_frames_bits read, frame type 1) into out_split[i] (uint8 [nb]),
+ *   out_mv[i] (int16 [nb][4][3], entries past the first of an unsplit block 0) and the plane
+ *   out_recon[i] (uint8 [H][W]).  qp, and qp_row[i] (int32 [H / bs]) / qp_map[i] (int32 [nb]) as
+ *   so_inter_recon_ex takes them; qp_row, qp_map or single entries may be NULL.
+ *   Reference list of frame i: the last min(nref_max, nref0 + i) planes of refs0[0..nref0)
+ *   followed by out_recon[0..i), oldest first -- the list decoder.decode_symbols hands to
+ *   so_inter_recon_ex for that frame.
+ *   Result: bit for bit that of so_unpack_frames(_bits) + so_inter_recon_ex(fme = 0) per frame,
+ *   for block size 16 (split blocks included) and 8, any H, W that are multiples of bs.
+ *   Malformed input: whatever so_unpack_frames(_bits) calls malformed, and -- new here -- a
+ *   reference index outside [0, the frame's list length) in any motion vector the block uses (its
+ *   first; all four when split).  A malformed block sets err[i] = 1 + its index (err: device int32
+ *   [nframes], zeroed by the caller), its own pixels, split and mv are unspecified, and nothing is
+ *   read or written outside the buffers given: the reference list is indexed only after the check,
+ *   and dx / dy need none (every sample outside the plane's interior is bounded one by one).
+ *   Every other block of the frame is decoded as usual, later frames run on whatever that left,
+ *   and the call returns SO_OK: the caller reads err.  Offsets that point outside packed[i]'s
+ *   buffer are a caller precondition, as for the unpack entry points.
+ *   Before any launch: SO_E_UNSUPPORTED for a bs other than 16 / 8; SO_E_INVALID for nframes < 0, a
+ *   coding other than 1 / 2, H or W not a positive multiple of bs, qp outside 0..20, nref_max
+ *   outside 1..SO_MAX_REF, nref0 outside 1..nref_max, a NULL required pointer, an out_recon[i]
+ *   that is not 16-byte aligned (out_mv[i]: 4-byte) or that aliases a refs0 plane or another
+ *   out_recon.  nframes == 0 with valid scalars is SO_OK.
+ *
+ * so_decode_chroma_frames: U and V of a run of frames of either type (frame_types[i]: 0 intra,
+ *   1 inter).  Frame i is decoded from its chroma records packed[i] / offs[i][0..nb] (the formats
+ *   of so_unpack_chroma_frames / _bits) and the luma split[i] / mv[i] of the same frame --
+ *   so_decode_p_frames' outputs, or an I-frame's unpacked ones; for a type-0 frame they are not
+ *   read and may be NULL (as may split / mv themselves when no frame is type 1).  qp, qp_row,
+ *   qp_map, qp_offset as so_chroma_recon_frame takes them.
+ *   Reference lists (U and V alike), the rule of decoder._chroma_loop: they start as refs0_u /
+ *   refs0_v[0..nref0); a P-frame predicts from the current list, an I-frame clears it first; every
+ *   reconstruction is then appended, the oldest dropped when the list holds nref_max.  nref0 may
+ *   be 0 only if frame 0 is type 0.
+ *   Result: bit for bit that of so_unpack_chroma_frames(_bits) + so_chroma_recon_frame per frame.
+ *   The reference index is clamped to the list, as so_chroma_recon_frame does.  A malformed record
+ *   sets err[i] = 1 + its index; its two blocks are not written.
+ *   Before any launch: SO_E_UNSUPPORTED for bs != 16; SO_E_INVALID as above, and for a frame type
+ *   other than 0 / 1, qp_offset outside -20..20, nref0 outside 0..nref_max, a P-frame whose list
+ *   is empty, planes that are not 8-byte aligned, an out_recon_u[i] equal to out_recon_v[i], or a
+ *   reconstruction that aliases a refs0 plane or another reconstruction.
+ */
+int so_decode_p_frames(int nframes, int coding, const uint8_t* const* packed,
+                       const uint32_t* const* offs, int H, int W, int bs, int qp,
+                       const int32_t* const* qp_row, const int32_t* const* qp_map,
+                       const uint8_t* const* refs0, int nref0, int nref_max,
+                       uint8_t* const* out_split, int16_t* const* out_mv, uint8_t* const* out_recon,
+                       int32_t* err, void* stream);
+int so_decode_chroma_frames(int nframes, int coding, const int32_t* frame_types,
+                            const uint8_t* const* packed, const uint32_t* const* offs, int H, int W,
+                            int bs, const uint8_t* const* split, const int16_t* const* mv, int qp,
+                            const int32_t* const* qp_row, const int32_t* const* qp_map,
+                            int qp_offset, const uint8_t* const* refs0_u,
+                            const uint8_t* const* refs0_v, int nref0, int nref_max,
+                            uint8_t* const* out_recon_u, uint8_t* const* out_recon_v, int32_t* err,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,9 @@ _SIGS = {
     "so_pack_chroma_frames_bits_after": ([_i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
     "so_unpack_chroma_frames": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "so_unpack_chroma_frames_bits": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
+    "so_decode_p_frames": ([_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "so_decode_chroma_frames": ([_i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i,
+                                 _vp, _vp, _vp, _vp], _i),
     "so_fme_plane_stride": ([_i, _i], _sz),
     "so_fme_workspace_bytes": ([_i, _i, _i], _sz),
     "so_fme_planes": ([_vp, _i, _i, _i, _vp, _vp], _i),

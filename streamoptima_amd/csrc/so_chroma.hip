@@ -24,56 +24,6 @@
 
 namespace so {
 
-SO_DEV int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// Four prediction samples of plane row Y starting at column X for the chroma MV (dx, dy) in
-// half-sample units.  Inside the plane (the lane's 5 x 2 footprint; every lane of a block whose
-// 9 x 9 footprint lies inside takes it) the two rows come as aligned dwords funnel-shifted to
-// the sample, as fetch_row does -- only dwords that hold a needed byte are read, so nothing
-// outside the plane is touched; otherwise every coordinate is clamped.
-SO_DEV void chroma_pred4(const uint8_t* __restrict__ R, int Wc, int Hc, int X, int Y, int dx, int dy, int* out) {
-    const int ix = dx >> 1, fx = dx & 1, iy = dy >> 1, fy = dy & 1;
-    const int xs = X + ix, ys = Y + iy;
-    if (xs >= 0 && xs + 3 + fx < Wc && ys >= 0 && ys + fy < Hc) {
-        uint32_t lo[2], hi[2];   // row y: samples 0..3, sample 4
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const uint8_t* p = R + (size_t)(ys + (r ? fy : 0)) * Wc + xs;
-            const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-            const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-            const uint32_t sh = (uint32_t)(a & 3);
-            const uint32_t w0 = q[0];
-            const uint32_t w1 = (sh + (uint32_t)fx) ? q[1] : 0u;   // holds a needed byte only then
-            lo[r] = __builtin_amdgcn_alignbyte(w1, w0, sh);
-            hi[r] = (w1 >> (8 * sh)) & 255u;   // byte sh + 4 of the pair
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t a0 = (lo[0] >> (8 * k)) & 255u, b0 = (lo[1] >> (8 * k)) & 255u;
-            const uint32_t a1n = k < 3 ? (lo[0] >> (8 * k + 8)) & 255u : hi[0];
-            const uint32_t b1n = k < 3 ? (lo[1] >> (8 * k + 8)) & 255u : hi[1];
-            const uint32_t a1 = fx ? a1n : a0, b1 = fx ? b1n : b0;
-            out[k] = (int)((a0 + a1 + b0 + b1 + 2u) >> 2);
-        }
-    } else {
-        const int y0 = clampi(ys, 0, Hc - 1), y1 = clampi(ys + fy, 0, Hc - 1);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int x0 = clampi(xs + k, 0, Wc - 1), x1 = clampi(xs + k + fx, 0, Wc - 1);
-            out[k] = ((int)R[(size_t)y0 * Wc + x0] + (int)R[(size_t)y0 * Wc + x1] + (int)R[(size_t)y1 * Wc + x0] +
-                      (int)R[(size_t)y1 * Wc + x1] + 2) >> 2;
-        }
-    }
-}
-
-SO_DEV const uint8_t* pick_ref(const RefSet& rs, int r) {
-    const uint8_t* p = rs.p[0];
-    p = r == 1 ? rs.p[1] : p;
-    p = r == 2 ? rs.p[2] : p;
-    p = r == 3 ? rs.p[3] : p;
-    return p;
-}
-
 template <bool ENC>
 __global__ void __launch_bounds__(256) chroma_kernel(const ChromaArgs a) {
     constexpr int N = 8, P = N + 1, G = 256 / N;

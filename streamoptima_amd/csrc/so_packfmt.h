@@ -280,6 +280,32 @@ SO_DEV void unpack_chroma_record(Reader& r, int16_t* qu, int16_t* qv) {
     r.finish();
 }
 
+// ---- what the fused decoders (so_decode.hip) add ------------------------------------------------
+// A P-frame's reference indices are input like any other number of the record: true when every
+// motion vector the block uses -- its first, or all four when split -- names a reference in
+// [0, nref).  A decoder indexes its reference list only after this holds.
+SO_DEV bool luma_mv_refs_ok(int split, const int16_t* mv, int nref) {
+    bool ok = true;
+    for (int j = 0; j < (split ? 4 : 1); ++j) ok = ok && mv[3 * j + 2] >= 0 && mv[3 * j + 2] < nref;
+    return ok;
+}
+
+// The fused decoders parse a workgroup's records into an LDS tile, one record per lane, kDecodeTile
+// records per workgroup.  A record's coefficients start decode_tile_stride int16 after the previous
+// record's: 8 int16 (4 dwords) of padding keep the 16-byte row loads of the transform phase aligned
+// and spread the parse lanes over 16 LDS banks instead of one.
+constexpr int kDecodeTile = 64;
+constexpr int decode_tile_stride(int ncoef) { return ncoef + 8; }
+
+// One luma P record into its tile slot q (zeroed by the caller): unpack_luma_record, then the
+// reference check.  Returns true when the record is malformed; split / mv / q are then unspecified
+// and must not be used.
+template <int BS, typename Reader>
+SO_DEV bool decode_luma_p_record(Reader& r, int nref, uint8_t* split, int16_t* mv, int16_t* q) {
+    unpack_luma_record<BS>(r, 1, split, mv, q);
+    return r.bad || !luma_mv_refs_ok(*split, mv, nref);
+}
+
 // =================================== device layer ==============================================
 #ifdef __HIPCC__
 

@@ -305,6 +305,25 @@ class decoder:
             self.decoded_vid = host
         return host
 
+    def decode_packed_stream(self, path: str, out_path: str | None = None, consume=None, chunk: int = 2,
+                             nbuf: int = 2) -> dict:
+        """decode_packed_file's frames without its footprint (hostdecode.HostStreamDecoder): the file
+        is read as it goes, P-frames and chroma are decoded from the packed records straight to
+        pixels (so_decode_p_frames, so_decode_chroma_frames), and upload, decode and download overlap
+        with a fixed set of buffers whatever the file's length.  out_path: write the frames as a
+        planar file (Y | U | V per frame; Y alone for a luma-only file) -- save_yuv420's /
+        save_decoded_frames' bytes.  consume(i, y, u, v): called per frame in order with host arrays
+        cropped to the picture, valid inside the call.  One of the two.  The stream decoder is kept
+        with this instance.  Returns {"frames", "frame_type", "coding", "layout"}."""
+        from .hostdecode import HostStreamDecoder
+        if (out_path is None) == (consume is None):
+            raise ValueError("decode_packed_stream: give out_path or consume")
+        key = (int(chunk), int(nbuf))
+        if getattr(self, "_stream_dec", None) is None or self._stream_dec[0] != key:
+            self._stream_dec = (key, HostStreamDecoder(self, chunk=chunk, nbuf=nbuf))
+        hs = self._stream_dec[1]
+        return hs.decode_to_yuv(path, out_path) if out_path is not None else hs.decode_file(path, consume)
+
     def save_decoded_frames(self, filename="yuv/decoded_bitstream_frames.yuv"):
         if not self.decoded_vid_f:
             print("[ERROR] No decoded frames available.")

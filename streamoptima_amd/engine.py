@@ -758,6 +758,110 @@ class Engine:
             raise ValueError(f"{name}: malformed packed chroma stream at record {bad - 1}")
         return [(q[i, 0], q[i, 1]) for i in range(n)]
 
+    # ---- fused decode (so_decode_p_frames / so_decode_chroma_frames) ---------------------------
+    @staticmethod
+    def _coding_number(coding: str) -> int:
+        return 2 if pack_coding_is_bits(coding) else 1
+
+    def _qp_ptrs(self, qps, n: int, what: str):
+        """Per-frame QP sources as a host array of device pointers: each entry None, a device
+        int32 tensor (used as it is) or a list (uploaded once per content, device_const_i32).
+        Returns (array or None, the tensors to keep alive)."""
+        if qps is None or all(q is None for q in qps):
+            return None, []
+        if len(qps) != n:
+            raise ValueError(f"{what}: {len(qps)} entries for {n} frames")
+        ts = [q if q is None or isinstance(q, torch.Tensor) else self.device_const_i32(list(q)) for q in qps]
+        for t in ts:
+            if t is not None and (t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous()):
+                raise ValueError(f"{what}: a contiguous int32 tensor on {self.device}")
+        return (ctypes.c_void_p * n)(*[_lib.ptr(t) for t in ts]), ts
+
+    def decode_p_frames(self, packed: list, offs: list, refs0: list, nref_max: int, qp: int, qp_rows=None,
+                        qp_maps=None, coding: str = "varint", out_split=None, out_mv=None, out_recon=None,
+                        err: torch.Tensor | None = None):
+        """so_decode_p_frames: a run of consecutive luma P-frames from their packed records
+        (device uint8) and block offsets (device int32 [nb + 1]) straight to reconstructions, no
+        dense coefficients in between.  refs0: the reference list before the run, oldest first;
+        frame i predicts from the last min(nref_max, len(refs0) + i) planes of refs0 + the run's
+        earlier reconstructions.  qp_rows / qp_maps: per frame None, a device int32 tensor
+        ([nby] / [nb]) or a list.  out_*: lists of tensors to write (allocated when None); err: a
+        zeroed device int32 [n] that receives 1 + a malformed block's index per frame (allocated
+        when None).  Asynchronous: nothing is read back -- the caller checks err.
+        Returns (split, mv, recon, err): three lists and the tensor."""
+        n = len(packed)
+        if len(offs) != n or n == 0:
+            raise ValueError("decode_p_frames: one offsets tensor per packed stream, at least one")
+        for o in offs:
+            if o.dtype != torch.int32 or o.numel() != self.nb + 1 or not o.is_contiguous():
+                raise ValueError(f"decode_p_frames: offs must be contiguous int32 [{self.nb + 1}]")
+        for k, r in enumerate(refs0):
+            self._check_plane(r, f"refs0[{k}]")
+        d = self.device
+        out_split = out_split or [torch.empty(self.nb, dtype=torch.uint8, device=d) for _ in range(n)]
+        out_mv = out_mv or [torch.empty((self.nb, 4, 3), dtype=torch.int16, device=d) for _ in range(n)]
+        out_recon = out_recon or list(alloc_planes(n, self.h, self.w, d))
+        for k, r in enumerate(out_recon):
+            self._check_plane(r, f"out_recon[{k}]")
+        err = torch.zeros(n, dtype=torch.int32, device=d) if err is None else err
+        if err.dtype != torch.int32 or err.numel() < n or err.device != d or not err.is_contiguous():
+            raise ValueError(f"decode_p_frames: err must be a contiguous int32 [{n}] on {d}")
+        qr, keep_r = self._qp_ptrs(qp_rows, n, "decode_p_frames qp_rows")
+        qm, keep_m = self._qp_ptrs(qp_maps, n, "decode_p_frames qp_maps")
+
+        def arr(ts):
+            return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        rc = self.lib.so_decode_p_frames(n, self._coding_number(coding), arr(packed), arr(offs), self.h, self.w,
+                                         self.bs, int(qp), qr, qm, arr(refs0) if refs0 else None, len(refs0),
+                                         int(nref_max), arr(out_split), arr(out_mv), arr(out_recon), err.data_ptr(),
+                                         _lib.stream_handle(d))
+        _lib.check(rc, "so_decode_p_frames")
+        return out_split, out_mv, out_recon, err
+
+    def decode_chroma_frames(self, frame_types: list, packed: list, offs: list, split: list, mv: list, refs0_u: list,
+                             refs0_v: list, nref_max: int, qp: int, qp_offset: int = 0, qp_rows=None, qp_maps=None,
+                             coding: str = "varint", out_u=None, out_v=None, err: torch.Tensor | None = None):
+        """so_decode_chroma_frames: U and V of a run of frames from their packed chroma records and
+        the frames' luma split / mv (None for an I-frame).  The reference lists start as refs0_u /
+        refs0_v, are cleared by an I-frame, take every reconstruction and hold at most nref_max
+        planes.  Other arguments as decode_p_frames.  Returns (recon_u, recon_v, err)."""
+        if self.fme:
+            raise NotImplementedError("chroma with FMEEnable: the luma MVs are in half-pel units")
+        n = len(packed)
+        if n == 0 or len(offs) != n or len(frame_types) != n or len(split) != n or len(mv) != n:
+            raise ValueError("decode_chroma_frames: one entry per frame in every list, at least one frame")
+        for o in offs:
+            if o.dtype != torch.int32 or o.numel() != self.nb + 1 or not o.is_contiguous():
+                raise ValueError(f"decode_chroma_frames: offs must be contiguous int32 [{self.nb + 1}]")
+        if len(refs0_u) != len(refs0_v):
+            raise ValueError(f"chroma: {len(refs0_u)} U references against {len(refs0_v)} V references")
+        for k, (ru, rv) in enumerate(zip(refs0_u, refs0_v)):
+            self._check_chroma_plane(ru, f"refs0_u[{k}]")
+            self._check_chroma_plane(rv, f"refs0_v[{k}]")
+        d = self.device
+        if out_u is None or out_v is None:
+            pl = alloc_planes(2 * n, self.h // 2, self.w // 2, d)
+            out_u, out_v = list(pl[:n]), list(pl[n:])
+        for k, (u, v) in enumerate(zip(out_u, out_v)):
+            self._check_chroma_plane(u, f"out_u[{k}]")
+            self._check_chroma_plane(v, f"out_v[{k}]")
+        err = torch.zeros(n, dtype=torch.int32, device=d) if err is None else err
+        if err.dtype != torch.int32 or err.numel() < n or err.device != d or not err.is_contiguous():
+            raise ValueError(f"decode_chroma_frames: err must be a contiguous int32 [{n}] on {d}")
+        qr, keep_r = self._qp_ptrs(qp_rows, n, "decode_chroma_frames qp_rows")
+        qm, keep_m = self._qp_ptrs(qp_maps, n, "decode_chroma_frames qp_maps")
+
+        def arr(ts):
+            return (ctypes.c_void_p * len(ts))(*[_lib.ptr(t) for t in ts])
+        types = (ctypes.c_int32 * n)(*[int(t) for t in frame_types])
+        rc = self.lib.so_decode_chroma_frames(n, self._coding_number(coding), types, arr(packed), arr(offs), self.h,
+                                              self.w, self.bs, arr(split), arr(mv), int(qp), qr, qm, int(qp_offset),
+                                              arr(refs0_u) if refs0_u else None, arr(refs0_v) if refs0_v else None,
+                                              len(refs0_u), int(nref_max), arr(out_u), arr(out_v), err.data_ptr(),
+                                              _lib.stream_handle(d))
+        _lib.check(rc, "so_decode_chroma_frames")
+        return out_u, out_v, err
+
     # ---- metrics ---------------------------------------------------------------------------
     def sum_rows(self, rows: list, out: torch.Tensor | None = None) -> torch.Tensor:
         """int64 [n]: the sum of each int32 tensor in `rows` (equal lengths), one launch."""

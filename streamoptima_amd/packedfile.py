@@ -121,6 +121,89 @@ def write(path: str, eng, symbols: list, qp_rows: list | None = None, coding: st
     return write_frames(path, eng.h, eng.w, eng.bs, eng.nb, coding, frames, chroma_qp_offset=qp_offset)
 
 
+def open_frames(path):
+    """The container read as it goes: -> (header, frames).  header: {"h", "w", "bs", "nb", "coding",
+    "layout", "nframes", "chroma" (bool), "has_qp_maps" (bool), "chroma_qp_offset" (None without
+    chroma)} -- read()'s fields without the per-frame lists.  frames: an iterator of one host record
+    per frame, {"frame_type", "qp_rows" (list), "block_bytes" (uint16 [nb]), "payload" (bytes),
+    "qp_map" (uint8 [nb] or None), "chroma_block_bytes", "chroma_payload" (None without chroma)}:
+    write_frames' input.  Nothing but the current frame's record is held, no read asks for more
+    than one section of a frame, and no device is touched.  The ValueErrors are read()'s -- bad
+    magic, version or flags here; lengths that do not add up, a file that ends inside a frame and
+    bytes after the last frame from the iterator, at the frame where they become visible (the
+    last frame is not yielded when bytes follow it).  path: a file name, or an open binary file
+    object (which is not closed)."""
+    own = not hasattr(path, "read")
+    f = open(path, "rb") if own else path
+    name = path if own else getattr(path, "name", "<file>")
+    try:
+        head = f.read(28)
+        if head[:4] != MAGIC:
+            raise ValueError(f"{name}: not a packed StreamOptima bitstream")
+        if len(head) < 28:
+            raise ValueError(f"{name}: the file ends inside the header")
+        version, h, w, bs, nframes, nb = struct.unpack_from("<6I", head, 4)
+        layout = version >> 16
+        coding = {v: c for c, v in VERSIONS.items()}.get(version & 0xFFFF)
+        if coding is None or layout > 1:
+            raise ValueError(f"{name}: container version {version}")
+        flags, qp_offset = 0, None
+        if layout == 1:
+            ext = f.read(8)
+            if len(ext) < 8:
+                raise ValueError(f"{name}: the file ends inside the header")
+            flags, qp_offset = struct.unpack("<Ii", ext)
+            if flags & ~(FLAG_CHROMA | FLAG_QP_MAPS):
+                raise ValueError(f"{name}: unknown container flags {flags:#x}")
+    except BaseException:
+        if own:
+            f.close()
+        raise
+    header = {"h": h, "w": w, "bs": bs, "nb": nb, "coding": coding, "layout": layout, "nframes": nframes,
+              "chroma": bool(flags & FLAG_CHROMA), "has_qp_maps": bool(flags & FLAG_QP_MAPS),
+              "chroma_qp_offset": qp_offset if flags & FLAG_CHROMA else None}
+
+    def take(n: int) -> bytes:
+        data = f.read(n) if n else b""
+        if len(data) != n:
+            raise ValueError(f"{name}: the file ends inside a frame")
+        return data
+
+    def section(what: str):
+        (nbytes,) = struct.unpack("<I", take(4))
+        lens = np.frombuffer(take(2 * nb), np.uint16)
+        if int(lens.astype(np.int64).sum()) != nbytes:
+            raise ValueError(f"{name}: {what} lengths do not add up to the frame's byte count")
+        return lens, take(nbytes)
+
+    def frames():
+        try:
+            for i in range(nframes):
+                ft, nqp = struct.unpack("<BH", take(3))
+                rec = {"frame_type": int(ft), "qp_rows": np.frombuffer(take(nqp), np.int8).astype(int).tolist()}
+                rec["block_bytes"], rec["payload"] = section("block")
+                rec["qp_map"] = None
+                if flags & FLAG_QP_MAPS:
+                    has = take(1)[0]
+                    if has > 1:
+                        raise ValueError(f"{name}: QP map marker {has}")
+                    if has:
+                        rec["qp_map"] = np.frombuffer(take(nb), np.uint8)
+                rec["chroma_block_bytes"] = rec["chroma_payload"] = None
+                if flags & FLAG_CHROMA:
+                    rec["chroma_block_bytes"], rec["chroma_payload"] = section("chroma record")
+                if i == nframes - 1 and f.read(1):
+                    raise ValueError(f"{name}: bytes after the last frame")
+                yield rec
+            if nframes == 0 and f.read(1):
+                raise ValueError(f"{name}: bytes after the last frame")
+        finally:
+            if own:
+                f.close()
+
+    return header, frames()
+
+
 def read(path: str, device) -> dict:
     """-> {"h", "w", "bs", "nb", "coding", "frame_types", "qp_rows", "packed": [device uint8],
     "offs": [device int32 [nb + 1]], "layout", "qp_maps", "chroma_packed", "chroma_offs",
