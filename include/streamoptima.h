@@ -631,6 +631,65 @@ int so_chroma_recon_frame(const uint8_t* const* refs_u, const uint8_t* const* re
                           const int16_t* qtc_v, uint8_t* out_recon_u, uint8_t* out_recon_v, void* stream);
 
 /*
+ * Colour conversion (build extension; DESIGN.md "Colour conversion"): 8-bit RGB to and from the
+ * padded 4:2:0 planes the chroma path codes, exact integers, one launch for a batch of frames,
+ * asynchronous on `stream`, no host synchronisation.  tests/colourref.py restates it in numpy.
+ *   matrix      SO_COLOUR_BT601 (Kr 0.299, Kb 0.114) or SO_COLOUR_BT709 (Kr 0.2126, Kb 0.0722)
+ *   full_range  1: Y and C in 0..255, yoff 0;  0: Y in 16..235, C in 16..240, yoff 16
+ *   arithmetic  int32 with 16 fractional bits; >> is the arithmetic shift (floor)
+ *   forward tables  F = rint(coef * 65536), then the G entry of each row takes what makes the Y row
+ *               sum to rint(ys * 65536) (ys = 1 or 219/255) and the chroma rows to 0.  Rows Y, Cb, Cr;
+ *               columns R, G, B:
+ *                 601 full     [19595, 38470, 7471] [-11058, -21710, 32768] [32768, -27439, -5329]
+ *                 601 limited  [16829, 33039, 6416] [-9714, -19070, 28784] [28784, -24103, -4681]
+ *                 709 full     [13933, 46871, 4732] [-7509, -25259, 32768] [32768, -29763, -3005]
+ *                 709 limited  [11966, 40254, 4064] [-6596, -22188, 28784] [28784, -26145, -2639]
+ *   forward     Y = clip((F_Y . (R, G, B) + (yoff << 16) + 32768) >> 16, 0, 255) per pixel.  The chroma
+ *               sample of the 2 x 2 luma cell at (2i, 2j) comes from the cell's sums SR, SG, SB, sited
+ *               at the cell's centre, with one rounding:
+ *                 C = clip((F_C . (SR, SG, SB) + (128 << 18) + (1 << 17)) >> 18, 0, 255)
+ *               (the clip matters: at full range pure red and pure blue reach 256).  Y goes to an
+ *               Hp x Wp plane of pitch Wp, U and V to Hp/2 x Wp/2 planes of pitch Wp/2, and every
+ *               sample outside the h x w picture area is written as 128 by the same launch.
+ *   inverse tables  J = rint(M * 65536), unadjusted, M the inverse of the real forward matrix
+ *               (255/219 and 255/224 included at limited range).  Rows R, G, B; columns Y - yoff,
+ *               U - 128, V - 128:
+ *                 601 full     [65536, 0, 91881] [65536, -22553, -46802] [65536, 116130, 0]
+ *                 601 limited  [76309, 0, 104597] [76309, -25675, -53279] [76309, 132201, 0]
+ *                 709 full     [65536, 0, 103206] [65536, -12276, -30679] [65536, 121609, 0]
+ *                 709 limited  [76309, 0, 117489] [76309, -13975, -34925] [76309, 138438, 0]
+ *   inverse     each chroma sample serves its 2 x 2 luma samples (replication, the adjoint of the
+ *               forward average):
+ *                 out_c = clip((J[c][0] (Y - yoff) + J[c][1] (U - 128) + J[c][2] (V - 128) + 32768) >> 16, 0, 255)
+ *               The picture area of the padded planes is read; h x w pixels are written.
+ *   int32       forward: |F| <= 46871 and a cell's sums are <= 1020, so |F_C . S| <= 3 * 46871 * 1020
+ *               < 2^28 and the offsets add < 2^26; the Y sum is below 2^25.  Inverse: |J| <= 138438 <
+ *               2^18 and |Y - yoff|, |U - 128|, |V - 128| <= 255, so the three products sum to less
+ *               than 3 * 2^26 < 2^28.  No intermediate leaves int32.
+ *   layouts     SO_LAYOUT_HWC: interleaved, pixel (y, x) at rgb + y * pitch + 3 x (pitch >= 3 w);
+ *               SO_LAYOUT_CHW: planar, channel c of pixel (y, x) at rgb + c * plane_stride + y * pitch
+ *               + x (pitch >= w; plane_stride is ignored for HWC).  Bytes, any alignment: a row
+ *               segment whose address is not a multiple of 4 is moved byte by byte, so a cropped view
+ *               of a larger picture converts in place.
+ *   rgb, y, u, v  HOST arrays of nframes device pointers.  Only the picture area of a source is read;
+ *               only the planes (forward) or the picture area of rgb (inverse) are written.
+ * SO_E_INVALID before any launch, the argument named in so_last_error: h or w odd or not positive; Hp
+ * or Wp odd or smaller than the picture; a pitch smaller than a row; a matrix, full_range or layout
+ * outside the values above; nframes < 0; a NULL pointer; a destination that overlaps another
+ * destination or a source.  nframes == 0 with valid scalars returns SO_OK.
+ */
+#define SO_COLOUR_BT601 0
+#define SO_COLOUR_BT709 1
+#define SO_LAYOUT_HWC 0
+#define SO_LAYOUT_CHW 1
+int so_rgb_to_yuv420(const uint8_t* const* rgb, int nframes, int h, int w, int layout, size_t pitch,
+                     size_t plane_stride, int matrix, int full_range, int Hp, int Wp, uint8_t* const* y,
+                     uint8_t* const* u, uint8_t* const* v, void* stream);
+int so_yuv420_to_rgb(const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v, int nframes,
+                     int Hp, int Wp, int h, int w, int matrix, int full_range, int layout, uint8_t* const* rgb,
+                     size_t pitch, size_t plane_stride, void* stream);
+
+/*
  * out[i] = sum of rows[i][0..len) (int32 -> int64) for i < n: the per-frame SSE of a GOP from
  * the encode kernels' per-block / per-row out_sse arrays (rows: a HOST array of device
  * pointers), one launch.

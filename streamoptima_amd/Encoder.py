@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import decoder as _decoder_mod
+from .colour import as_colour, rgb_shape
 from .engine import Engine, FrameSymbols, alloc_planes
 from .blockapi import BlockAPI
 from .bitstream import (differential_encoder_frame as _diff_enc, entropy_encoder_block as _ent_blk,
@@ -52,7 +53,7 @@ class Y_Video_codec(BlockAPI):
                  lam=None, VBSEnable=False, nRefFrames=1, yuv_file=None, y_only_frame_arr=None,
                  fast_me=False, FMEEnable=False, RCFlag=None, targetBR=None, frame_rate=30,
                  qp_rate_tables=None, intra_thresh=None, ParallelMode=0, device=None, roi=None, qp_clamp=(0, 12),
-                 ssim=False, chroma=False, chroma_qp_offset=0, uv_frame_arr=None):
+                 ssim=False, chroma=False, chroma_qp_offset=0, uv_frame_arr=None, rgb_frame_arr=None, colour=None):
         if chroma and FMEEnable:
             raise NotImplementedError("chroma with FMEEnable is not built: the luma MVs are in half-pel units there")
         if chroma and block_size != 16:
@@ -136,6 +137,22 @@ class Y_Video_codec(BlockAPI):
                     raise ValueError(f"uv_frame_arr must be [F, 2, {h_pixels // 2}, {w_pixels // 2}], got "
                                      f"{tuple(uv_frame_arr.shape)}")
             self.uv_f_arr = uv_frame_arr
+        # build extension (DESIGN.md "Colour conversion"): rgb_frame_arr = [F, h, w, 3] uint8 frames in
+        # place of Y, U and V; encode() converts them on the device (so_rgb_to_yuv420) with `colour`
+        # (colour.Colour; None: BT.601, full range).  Left at None nothing is allocated or launched.
+        self.colour = as_colour(colour)
+        self.rgb_f_arr = None
+        if rgb_frame_arr is not None:
+            if not self.chroma:
+                raise ValueError("rgb_frame_arr needs chroma=True (RGB for a luma-only codec is not built)")
+            if yuv_file is not None or y_only_frame_arr is not None or uv_frame_arr is not None:
+                raise ValueError("rgb_frame_arr stands in place of yuv_file, y_only_frame_arr and uv_frame_arr")
+            rgb_frame_arr = np.asarray(rgb_frame_arr)
+            if (rgb_frame_arr.dtype != np.uint8 or rgb_frame_arr.ndim != 4
+                    or tuple(rgb_frame_arr.shape[1:]) != (h_pixels, w_pixels, 3)):
+                raise ValueError(f"rgb_frame_arr must be uint8 [F, {h_pixels}, {w_pixels}, 3], got "
+                                 f"{rgb_frame_arr.dtype} {tuple(rgb_frame_arr.shape)}")
+            self.rgb_f_arr = rgb_frame_arr
         self.chroma_symbols = None
         self.psnr_per_frame_u = self.psnr_per_frame_v = None
         self.decoded_chroma_device = None
@@ -423,9 +440,14 @@ class Y_Video_codec(BlockAPI):
             raise NotImplementedError("only intra_mode 0 is built")
         t0 = time.time()
         eng = self.engine()
-        frames_dev = self._upload_padded(self.y_only_f_arr[: self.frames])
         uv_dev = None
-        if self.chroma:
+        if self.rgb_f_arr is not None:
+            # the RGB frames as they are (3 B / pixel up), converted and padded by one launch
+            rgb_dev = torch.from_numpy(np.ascontiguousarray(self.rgb_f_arr[: self.frames])).to(self.device)
+            frames_dev, uv_dev = eng.rgb_to_yuv420(rgb_dev, self.colour)
+        else:
+            frames_dev = self._upload_padded(self.y_only_f_arr[: self.frames])
+        if self.chroma and uv_dev is None:
             if self.uv_f_arr is None:
                 raise ValueError("chroma=True needs uv_frame_arr or a yuv_file")
             uv_dev = self._upload_uv_padded(self.uv_f_arr[: self.frames])
@@ -638,6 +660,24 @@ class Y_Video_codec(BlockAPI):
             res.update(self._encode_chroma_gop(eng, uv_dev, out_syms, chroma_symbols))
         return res
 
+    def encode_device_rgb(self, rgb_dev: torch.Tensor, intra_dur: int, layout: str = "hwc", **kw):
+        """encode_device on RGB pictures held by the device: uint8 [F, h, w, 3] ("hwc") or
+        [F, 3, h, w] ("chw") at picture size, or cropped views of larger ones.  One
+        so_rgb_to_yuv420 launch (the codec's `colour`) makes the padded Y, U and V planes on the
+        current stream; **kw go to encode_device.  Needs chroma=True.  The result also holds the
+        converted planes as "frames_dev" and "uv_dev"."""
+        if not self.chroma:
+            raise ValueError("encode_device_rgb needs chroma=True (RGB for a luma-only codec is not built)")
+        if "uv_dev" in kw:
+            raise ValueError("encode_device_rgb makes the chroma planes itself: uv_dev is not an argument")
+        if tuple(rgb_dev.shape[-3:]) != rgb_shape(0, self.h_pixels, self.w_pixels, layout)[1:]:
+            raise ValueError(f"encode_device_rgb: {layout} pictures of {self.w_pixels}x{self.h_pixels} expected, got "
+                             f"{list(rgb_dev.shape)}")
+        frames_dev, uv_dev = self.engine().rgb_to_yuv420(rgb_dev, self.colour, layout)
+        res = self.encode_device(frames_dev, intra_dur, uv_dev=uv_dev, **kw)
+        res["frames_dev"], res["uv_dev"] = frames_dev, uv_dev
+        return res
+
     def _ssim_device(self, eng, frames_dev, syms) -> torch.Tensor:
         """SSIM of every frame of a GOP against its reconstruction, picture area only."""
         return eng.ssim([frames_dev[i] for i in range(len(syms))], [s.recon for s in syms], self.h_pixels,
@@ -720,6 +760,18 @@ class Y_Video_codec(BlockAPI):
                 f.write(s.recon.cpu().numpy()[:h, :w].tobytes())
                 f.write(c.recon_u.cpu().numpy()[: h // 2, : w // 2].tobytes())
                 f.write(c.recon_v.cpu().numpy()[: h // 2, : w // 2].tobytes())
+
+    def save_rgb(self, filename):
+        """The encoder's reconstruction as raw RGB24 (R, G, B per pixel, rows top down, frame after
+        frame) at picture size, converted on the device with the codec's `colour`
+        (so_yuv420_to_rgb).  Needs chroma=True and a finished encode()."""
+        if not self.chroma or self._symbols is None or self.chroma_symbols is None:
+            raise ValueError("save_rgb needs chroma=True and encode() first")
+        rgb = self.engine().yuv420_to_rgb([s.recon for s in self._symbols],
+                                          [(c.recon_u, c.recon_v) for c in self.chroma_symbols],
+                                          self.h_pixels, self.w_pixels, self.colour)
+        with open(filename, "wb") as f:
+            f.write(rgb.cpu().numpy().tobytes())
 
     def save_y_only(self, filename, y_data_list):
         with open(filename, "wb") as f:

@@ -62,6 +62,8 @@ _SIGS = {
     "so_chroma_encode_frame": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp], _i),
     "so_chroma_recon_frame": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "so_rgb_to_yuv420": ([_vp, _i, _i, _i, _i, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
+    "so_yuv420_to_rgb": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _sz, _vp], _i),
     "so_block_xform": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "so_encode_p_run_stripe": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_uint32, _i, _vp], _i),
@@ -125,6 +127,9 @@ OPT_RUN_2PASS_FUSED, OPT_FASTME_SERIAL, OPT_FASTME_SEGMENT, OPT_FASTME_WARMUP, O
 OPT_RUN_ZERO_SKIP = 7
 OPT_RUN_TALL_TILES = 8   # -1 (default): chosen per launch, 0: never, 1: always
 OPT_TEST_LOSE_FLAG = 6
+# so_rgb_to_yuv420 / so_yuv420_to_rgb (include/streamoptima.h SO_COLOUR_*, SO_LAYOUT_*)
+COLOUR_MATRICES = {"bt601": 0, "bt709": 1}
+COLOUR_LAYOUTS = {"hwc": 0, "chw": 1}
 
 EXPORTED = tuple(_SIGS)
 

@@ -6,12 +6,14 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <vector>
 
 #include <hip/hip_ext.h>
 
 #include "so_chroma.h"
+#include "so_colour.h"
 #include "so_common.h"
 #include "so_packfmt.h"
 #include "so_run.h"
@@ -1185,6 +1187,158 @@ int so_ssim_u8(const uint8_t* const* a, const uint8_t* const* b, int nframes, in
         SO_NEED(a[i], fn); SO_NEED(b[i], fn);
     }
     return ssim_launch(a, b, nframes, H, W, pitch_a, pitch_b, win, out, workspace, (hipStream_t)stream);
+}
+
+// ---- colour conversion (so_colour.hip) ------------------------------------------------------------
+namespace {
+struct ColourSpan {
+    uintptr_t lo, hi;   // [lo, hi)
+    bool dst;
+    const char* what;
+    int frame;
+};
+
+// two h-row views of `row` bytes per row and one pitch: does a byte belong to both?
+bool colour_views_overlap(uintptr_t a, uintptr_t b, size_t pitch, size_t row, int h) {
+    const uintptr_t d = a < b ? b - a : a - b;
+    const size_t q = d / pitch, r = d % pitch;
+    return (r < row && q < (size_t)h) || (r + row > pitch && q + 1 < (size_t)h);
+}
+
+// the scalar checks both directions share; fills g
+int colour_geom(const char* fn, int nframes, int h, int w, int Hp, int Wp, int layout, size_t pitch,
+                size_t plane_stride, int matrix, int full_range, bool forward, ColourGeom* g) {
+    if (h <= 0 || w <= 0 || h % 2 || w % 2) {
+        set_error("%s: h %d, w %d (a 4:2:0 picture is positive and even both ways)", fn, h, w);
+        return SO_E_INVALID;
+    }
+    if (Hp < h || Wp < w || Hp % 2 || Wp % 2) {
+        set_error("%s: Hp %d, Wp %d (even, and at least the picture's %d x %d)", fn, Hp, Wp, h, w);
+        return SO_E_INVALID;
+    }
+    if ((long long)Hp * Wp > (1ll << 31)) {
+        set_error("%s: Hp %d x Wp %d: frame too large", fn, Hp, Wp);
+        return SO_E_INVALID;
+    }
+    if (layout != SO_LAYOUT_HWC && layout != SO_LAYOUT_CHW) {
+        set_error("%s: layout %d (SO_LAYOUT_HWC or SO_LAYOUT_CHW)", fn, layout);
+        return SO_E_INVALID;
+    }
+    const size_t row = layout == SO_LAYOUT_HWC ? 3 * (size_t)w : (size_t)w;
+    if (pitch < row) {
+        set_error("%s: pitch %zu below a row's %zu bytes", fn, pitch, row);
+        return SO_E_INVALID;
+    }
+    if (layout == SO_LAYOUT_CHW && plane_stride == 0) {
+        set_error("%s: plane_stride 0 (the three planes of a CHW picture are apart)", fn);
+        return SO_E_INVALID;
+    }
+    if (matrix != SO_COLOUR_BT601 && matrix != SO_COLOUR_BT709) {
+        set_error("%s: matrix %d (SO_COLOUR_BT601 or SO_COLOUR_BT709)", fn, matrix);
+        return SO_E_INVALID;
+    }
+    if (full_range != 0 && full_range != 1) {
+        set_error("%s: full_range %d (0 or 1)", fn, full_range);
+        return SO_E_INVALID;
+    }
+    if (nframes < 0) {
+        set_error("%s: nframes %d", fn, nframes);
+        return SO_E_INVALID;
+    }
+    g->h = h; g->w = w; g->Hp = Hp; g->Wp = Wp;
+    g->pitch = pitch;
+    g->plane = layout == SO_LAYOUT_CHW ? plane_stride : 0;
+    const int32_t* t = (forward ? kColourFwd : kColourInv)[2 * matrix + (full_range ? 0 : 1)];
+    for (int i = 0; i < 9; ++i) g->c[i] = t[i];
+    g->yoff = full_range ? 0 : 16;
+    return SO_OK;
+}
+
+// Pointers and aliasing.  The planes are dense; an RGB picture is h rows of `row` bytes `pitch`
+// apart (three such views plane_stride apart for CHW).  A destination may share no byte with a
+// source or another destination.  Sources may repeat.
+int colour_alias(const char* fn, const uint8_t* const* rgb, const uint8_t* const* y, const uint8_t* const* u,
+                 const uint8_t* const* v, int nframes, const ColourGeom& g, int layout, bool forward) {
+    const size_t row = layout == SO_LAYOUT_HWC ? 3 * (size_t)g.w : (size_t)g.w;
+    const size_t view = (size_t)(g.h - 1) * g.pitch + row;
+    const size_t ny = (size_t)g.Hp * g.Wp, nc = ny / 4;
+    const int nviews = layout == SO_LAYOUT_HWC ? 1 : 3;
+    std::vector<ColourSpan> spans;
+    spans.reserve((size_t)nframes * 6);
+    for (int i = 0; i < nframes; ++i) {
+        const uintptr_t py = reinterpret_cast<uintptr_t>(y[i]), pu = reinterpret_cast<uintptr_t>(u[i]),
+                        pv = reinterpret_cast<uintptr_t>(v[i]), pr = reinterpret_cast<uintptr_t>(rgb[i]);
+        spans.push_back({py, py + ny, forward, "y", i});
+        spans.push_back({pu, pu + nc, forward, "u", i});
+        spans.push_back({pv, pv + nc, forward, "v", i});
+        for (int c = 0; c < nviews; ++c)
+            spans.push_back({pr + c * g.plane, pr + c * g.plane + view, !forward, "rgb", i});
+    }
+    std::sort(spans.begin(), spans.end(), [](const ColourSpan& a, const ColourSpan& b) { return a.lo < b.lo; });
+    // the furthest end so far of a source, of a destination, and which span it belongs to
+    const ColourSpan *far_src = nullptr, *far_dst = nullptr;
+    for (const ColourSpan& s : spans) {
+        const ColourSpan* hit = nullptr;
+        if (far_dst && s.lo < far_dst->hi && (!s.dst || forward)) hit = far_dst;   // inverse: dst vs dst below
+        if (!hit && s.dst && far_src && s.lo < far_src->hi) hit = far_src;
+        if (hit) {
+            set_error("%s: %s[%d] aliases %s[%d] (a destination overlaps a source or another destination)", fn,
+                      s.what, s.frame, hit->what, hit->frame);
+            return SO_E_INVALID;
+        }
+        const ColourSpan*& far = s.dst ? far_dst : far_src;
+        if (!far || s.hi > far->hi) far = &s;
+    }
+    if (!forward) {
+        // RGB destinations may interleave row by row (crops of one canvas): an exact test, pair by pair
+        std::vector<uintptr_t> views;
+        for (int i = 0; i < nframes; ++i)
+            for (int c = 0; c < nviews; ++c) views.push_back(reinterpret_cast<uintptr_t>(rgb[i]) + c * g.plane);
+        for (size_t a = 0; a < views.size(); ++a)
+            for (size_t b = a + 1; b < views.size(); ++b)
+                if (colour_views_overlap(views[a], views[b], g.pitch, row, g.h)) {
+                    set_error("%s: rgb[%d] aliases rgb[%d] (two destination pictures share bytes)", fn,
+                              (int)(a / nviews), (int)(b / nviews));
+                    return SO_E_INVALID;
+                }
+    }
+    return SO_OK;
+}
+
+int colour_pointers(const char* fn, const uint8_t* const* rgb, const uint8_t* const* y, const uint8_t* const* u,
+                    const uint8_t* const* v, int nframes) {
+    SO_NEED(rgb, fn); SO_NEED(y, fn); SO_NEED(u, fn); SO_NEED(v, fn);
+    for (int i = 0; i < nframes; ++i)
+        if (!rgb[i] || !y[i] || !u[i] || !v[i]) {
+            set_error("%s: %s[%d] is NULL", fn, !rgb[i] ? "rgb" : !y[i] ? "y" : !u[i] ? "u" : "v", i);
+            return SO_E_INVALID;
+        }
+    return SO_OK;
+}
+}  // namespace
+
+int so_rgb_to_yuv420(const uint8_t* const* rgb, int nframes, int h, int w, int layout, size_t pitch,
+                     size_t plane_stride, int matrix, int full_range, int Hp, int Wp, uint8_t* const* y,
+                     uint8_t* const* u, uint8_t* const* v, void* stream) {
+    const char* fn = "so_rgb_to_yuv420";
+    ColourGeom g{};
+    SO_TRY(colour_geom(fn, nframes, h, w, Hp, Wp, layout, pitch, plane_stride, matrix, full_range, true, &g));
+    if (nframes == 0) return SO_OK;
+    SO_TRY(colour_pointers(fn, rgb, y, u, v, nframes));
+    SO_TRY(colour_alias(fn, rgb, y, u, v, nframes, g, layout, true));
+    return colour_forward_launch(layout, rgb, y, u, v, nframes, g, (hipStream_t)stream);
+}
+
+int so_yuv420_to_rgb(const uint8_t* const* y, const uint8_t* const* u, const uint8_t* const* v, int nframes,
+                     int Hp, int Wp, int h, int w, int matrix, int full_range, int layout, uint8_t* const* rgb,
+                     size_t pitch, size_t plane_stride, void* stream) {
+    const char* fn = "so_yuv420_to_rgb";
+    ColourGeom g{};
+    SO_TRY(colour_geom(fn, nframes, h, w, Hp, Wp, layout, pitch, plane_stride, matrix, full_range, false, &g));
+    if (nframes == 0) return SO_OK;
+    SO_TRY(colour_pointers(fn, rgb, y, u, v, nframes));
+    SO_TRY(colour_alias(fn, rgb, y, u, v, nframes, g, layout, false));
+    return colour_inverse_launch(layout, y, u, v, rgb, nframes, g, (hipStream_t)stream);
 }
 
 // ---- chroma 4:2:0 (so_chroma.hip) ----------------------------------------------------------------

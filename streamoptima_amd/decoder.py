@@ -306,23 +306,34 @@ class decoder:
         return host
 
     def decode_packed_stream(self, path: str, out_path: str | None = None, consume=None, chunk: int = 2,
-                             nbuf: int = 2) -> dict:
+                             nbuf: int = 2, output: str = "yuv420", colour=None) -> dict:
         """decode_packed_file's frames without its footprint (hostdecode.HostStreamDecoder): the file
         is read as it goes, P-frames and chroma are decoded from the packed records straight to
         pixels (so_decode_p_frames, so_decode_chroma_frames), and upload, decode and download overlap
         with a fixed set of buffers whatever the file's length.  out_path: write the frames as a
         planar file (Y | U | V per frame; Y alone for a luma-only file) -- save_yuv420's /
         save_decoded_frames' bytes.  consume(i, y, u, v): called per frame in order with host arrays
-        cropped to the picture, valid inside the call.  One of the two.  The stream decoder is kept
-        with this instance.  Returns {"frames", "frame_type", "coding", "layout"}."""
+        cropped to the picture, valid inside the call.  One of the two.  output="rgb" (with `colour`,
+        a colour.Colour; None: BT.601, full range) converts every frame on the device: the file is
+        then raw RGB24 and the call consume(i, rgb) with rgb [h, w, 3]; a luma-only file raises
+        ValueError.  The stream decoder is kept with this instance.  Returns {"frames",
+        "frame_type", "coding", "layout"}."""
+        from .colour import as_colour
         from .hostdecode import HostStreamDecoder
         if (out_path is None) == (consume is None):
             raise ValueError("decode_packed_stream: give out_path or consume")
-        key = (int(chunk), int(nbuf))
+        key = (int(chunk), int(nbuf), output, as_colour(colour))
         if getattr(self, "_stream_dec", None) is None or self._stream_dec[0] != key:
-            self._stream_dec = (key, HostStreamDecoder(self, chunk=chunk, nbuf=nbuf))
+            self._stream_dec = (key, HostStreamDecoder(self, chunk=chunk, nbuf=nbuf, output=output, colour=colour))
         hs = self._stream_dec[1]
-        return hs.decode_to_yuv(path, out_path) if out_path is not None else hs.decode_file(path, consume)
+        if out_path is None:
+            return hs.decode_file(path, consume)
+        return hs.decode_to_rgb(path, out_path) if output == "rgb" else hs.decode_to_yuv(path, out_path)
+
+    def decode_to_rgb(self, path: str, out_path: str, colour=None, chunk: int = 2, nbuf: int = 2) -> dict:
+        """The packed file at `path` as raw RGB24 at picture size, frame after frame:
+        decode_packed_stream with output="rgb"."""
+        return self.decode_packed_stream(path, out_path=out_path, chunk=chunk, nbuf=nbuf, output="rgb", colour=colour)
 
     def save_decoded_frames(self, filename="yuv/decoded_bitstream_frames.yuv"):
         if not self.decoded_vid_f:

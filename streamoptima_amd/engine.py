@@ -888,6 +888,62 @@ class Engine:
             ws = self._ssim_ws = torch.empty(max(need, 1), dtype=torch.float64, device=self.device)
         return ssim_planes(self.lib, self.device, a_planes, b_planes, h, w, win, out, ws)
 
+    # ---- colour conversion (so_colour.hip) ---------------------------------------------------
+    def rgb_to_yuv420(self, rgb: torch.Tensor, colour=None, layout: str = "hwc", out_y: torch.Tensor | None = None,
+                      out_uv: torch.Tensor | None = None):
+        """8-bit RGB pictures -> (y [F, Hp, Wp], uv [F, 2, Hp/2, Wp/2]): the engine's padded planes
+        in alloc_planes layout, every sample outside the picture 128, one so_rgb_to_yuv420 launch on
+        the current stream, no host synchronisation.  rgb: uint8 [F, h, w, 3] ("hwc") or
+        [F, 3, h, w] ("chw") on the device, h and w even and at most the engine's size; a cropped
+        view of a larger picture converts in place (colour.rgb_pointers).  colour: a colour.Colour
+        (None: BT.601, full range).  out_y / out_uv: planes to write, of exactly those shapes."""
+        from . import colour as _colour
+        col = _colour.as_colour(colour)
+        ptrs, n, h, w, pitch, plane = _colour.rgb_pointers(rgb, layout, self.device)
+        hp, wp = self.h, self.w
+        if h % 2 or w % 2 or h > hp or w > wp:
+            raise ValueError(f"rgb_to_yuv420: a {w}x{h} picture (even, at most the engine's {wp}x{hp})")
+        if out_y is None:
+            out_y = alloc_planes(n, hp, wp, self.device)
+        if out_uv is None:
+            out_uv = alloc_planes(2 * n, hp // 2, wp // 2, self.device).view(n, 2, hp // 2, wp // 2)
+        py = _colour.plane_pointers(out_y, n, (hp, wp), self.device, "rgb_to_yuv420 out_y")
+        pu = _colour.plane_pointers([t[0] for t in out_uv], n, (hp // 2, wp // 2), self.device, "rgb_to_yuv420 out_uv")
+        pv = _colour.plane_pointers([t[1] for t in out_uv], n, (hp // 2, wp // 2), self.device, "rgb_to_yuv420 out_uv")
+        rc = self.lib.so_rgb_to_yuv420(ptrs, n, h, w, _colour.layout_code(layout), pitch, plane, col.matrix_code,
+                                       int(col.full_range), hp, wp, py, pu, pv, _lib.stream_handle(self.device))
+        _lib.check(rc, "so_rgb_to_yuv420")
+        return out_y, out_uv
+
+    def yuv420_to_rgb(self, y, uv, h: int, w: int, colour=None, layout: str = "hwc",
+                      out: torch.Tensor | None = None) -> torch.Tensor:
+        """The inverse: the h x w picture area of padded planes -> uint8 [F, h, w, 3] ("hwc") or
+        [F, 3, h, w] ("chw"), one so_yuv420_to_rgb launch on the current stream.  y: [F, Hp, Wp] or
+        a sequence of [Hp, Wp] planes; uv: [F, 2, Hp/2, Wp/2] or a sequence of (u, v) plane pairs
+        (Hp, Wp: the engine's size).  out: a tensor or view of the result's shape to write into."""
+        from . import colour as _colour
+        col = _colour.as_colour(colour)
+        hp, wp = self.h, self.w
+        h, w = int(h), int(w)
+        if h <= 0 or w <= 0 or h % 2 or w % 2 or h > hp or w > wp:
+            raise ValueError(f"yuv420_to_rgb: a {w}x{h} picture (even, at most the engine's {wp}x{hp})")
+        ys, uvs = list(y), list(uv)
+        n = len(ys)
+        if len(uvs) != n:
+            raise ValueError(f"yuv420_to_rgb: {n} luma planes, {len(uvs)} chroma pairs")
+        if out is None:
+            out = torch.empty(_colour.rgb_shape(n, h, w, layout), dtype=torch.uint8, device=self.device)
+        ptrs, on, oh, ow, pitch, plane = _colour.rgb_pointers(out, layout, self.device, "yuv420_to_rgb out")
+        if (on, oh, ow) != (n, h, w):
+            raise ValueError(f"yuv420_to_rgb: out holds {on} pictures of {ow}x{oh}, not {n} of {w}x{h}")
+        py = _colour.plane_pointers(ys, n, (hp, wp), self.device, "yuv420_to_rgb y")
+        pu = _colour.plane_pointers([t[0] for t in uvs], n, (hp // 2, wp // 2), self.device, "yuv420_to_rgb uv")
+        pv = _colour.plane_pointers([t[1] for t in uvs], n, (hp // 2, wp // 2), self.device, "yuv420_to_rgb uv")
+        rc = self.lib.so_yuv420_to_rgb(py, pu, pv, n, hp, wp, h, w, col.matrix_code, int(col.full_range),
+                                       _colour.layout_code(layout), ptrs, pitch, plane, _lib.stream_handle(self.device))
+        _lib.check(rc, "so_yuv420_to_rgb")
+        return out
+
     def sse_into(self, a: torch.Tensor, b: torch.Tensor, acc: torch.Tensor) -> None:
         """acc (uint64 view of an int64 device scalar) += sum((a-b)^2)."""
         rc = self.lib.so_sse_u8(a.data_ptr(), b.data_ptr(), a.numel(), acc.data_ptr(),

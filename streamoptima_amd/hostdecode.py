@@ -19,6 +19,9 @@ there.  One dense symbol set serves every I-frame (and, with FMEEnable, every P-
 kernel does not predict from the half-pel planes, so those go through so_unpack_frames +
 so_inter_recon_ex).
 
+With output="rgb" the compute stream ends a unit by converting its planes (so_yuv420_to_rgb) and
+copy stream B brings down one [chunk, h, w, 3] buffer in place of the Y, U and V planes.
+
 Reconstructions live in a ring of planes: a plane is written again only after its download
 event (the compute stream waits for it) and, by stream order, after its last use as a reference.
 """
@@ -30,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib, packedfile
+from .colour import as_colour
 from .engine import alloc_planes, pack_coding_is_bits
 from .hostmem import pinned_empty
 from .hwqueue import dedicated_stream
@@ -49,19 +53,32 @@ class _Set:
         self.offs = torch.zeros((c, eng.nb + 1), dtype=torch.int32, device=dev)     # [:, 0] stays 0
         self.coffs = torch.zeros((c, eng.nb + 1), dtype=torch.int32, device=dev)
         self.err = torch.zeros((2, c), dtype=torch.int32, device=dev)               # luma row, chroma row
-        self.y_h = pinned_empty((c, eng.h, eng.w))
-        self.uv_h = pinned_empty((c, 2, eng.h // 2, eng.w // 2)) if hs.chroma_ok else None
+        if hs.output == "rgb":
+            # the unit's pictures, converted on the compute stream, and their one host copy
+            hp, wp = int(hs.dec.h_pixels), int(hs.dec.w_pixels)
+            self.rgb_d = torch.empty((c, hp, wp, 3), dtype=torch.uint8, device=dev)
+            self.rgb_h = pinned_empty((c, hp, wp, 3))
+        else:
+            self.y_h = pinned_empty((c, eng.h, eng.w))
+            self.uv_h = pinned_empty((c, 2, eng.h // 2, eng.w // 2)) if hs.chroma_ok else None
         self.frames = []          # the unit: (index, frame type, bytes, chroma bytes, rows?, map?, plane)
         self.down = None          # D2H event of the unit
 
 
 class HostStreamDecoder:
-    def __init__(self, dec, chunk: int = 2, nbuf: int = 2, fused: bool = True):
+    def __init__(self, dec, chunk: int = 2, nbuf: int = 2, fused: bool = True, output: str = "yuv420", colour=None):
         """dec: a `decoder` (its geometry, Qp, nRefFrames, RCFlag, FMEEnable).  chunk: P-frames
         per unit; nbuf: units in flight.  fused=False decodes P-frames and chroma with the unpack
         and reconstruction kernels on the one dense symbol set instead of the fused kernels (the
-        same frames; tools/decode_time.py compares the two).  Every device and page-locked buffer
-        is allocated here."""
+        same frames; tools/decode_time.py compares the two).  output: "yuv420" = Y, U and V planes
+        to the host; "rgb" = each unit's planes converted on the compute stream (so_yuv420_to_rgb
+        with `colour`, a colour.Colour; None: BT.601, full range) and one [chunk, h, w, 3] buffer
+        downloaded in their place.  Every device and page-locked buffer is allocated here."""
+        if output not in ("yuv420", "rgb"):
+            raise ValueError(f"output {output!r} (\"yuv420\" or \"rgb\")")
+        self.output, self.colour = output, as_colour(colour)
+        if output == "rgb" and (dec.h_pixels % 2 or dec.w_pixels % 2):
+            raise ValueError(f"output=\"rgb\" needs an even picture size, got {dec.w_pixels}x{dec.h_pixels}")
         self.fused = bool(fused)
         eng = dec._eng()
         self.dec, self.eng, self.dev = dec, eng, eng.device
@@ -71,6 +88,8 @@ class HostStreamDecoder:
             raise ValueError(f"nRefFrames {self.nref} outside [1, {_lib.MAX_REF}]")
         self.fme = bool(dec.FMEEnable)
         self.chroma_ok = eng.bs == 16 and not self.fme
+        if output == "rgb" and not self.chroma_ok:
+            raise NotImplementedError("output=\"rgb\" needs chroma, which needs block_size 16 and no FMEEnable")
         nb, nby, c = eng.nb, eng.nby, self.chunk
         # a frame's staging slot: u16 lengths | u16 chroma lengths | i32 row QPs | i32 QP map | luma
         # bytes | chroma bytes (the chroma bytes start 16-aligned behind the luma bytes, so one copy
@@ -249,14 +268,20 @@ class HostStreamDecoder:
                                          rows, maps, coding=coding, out_u=cu, out_v=cv, err=s.err[1])
                 state["refs_u"] = (state["refs_u"] + cu)[-self.nref:]
                 state["refs_v"] = (state["refs_v"] + cv)[-self.nref:]
+            if self.output == "rgb":
+                eng.yuv420_to_rgb(outs, [self.cplanes[p] for p in ps], self.dec.h_pixels, self.dec.w_pixels,
+                                  self.colour, out=s.rgb_d[:n])
             done = torch.cuda.Event()
             done.record(comp)
         with torch.cuda.stream(self.d2h):
             self.d2h.wait_event(done)
-            for j, p in enumerate(ps):
-                s.y_h[j].copy_(self.planes[p], non_blocking=True)
-                if chroma:
-                    s.uv_h[j].copy_(self.cplanes[p], non_blocking=True)
+            if self.output == "rgb":
+                s.rgb_h[:n].copy_(s.rgb_d[:n], non_blocking=True)
+            else:
+                for j, p in enumerate(ps):
+                    s.y_h[j].copy_(self.planes[p], non_blocking=True)
+                    if chroma:
+                        s.uv_h[j].copy_(self.cplanes[p], non_blocking=True)
             self.err_h[k].copy_(s.err, non_blocking=True)
             s.down = torch.cuda.Event()
             s.down.record(self.d2h)
@@ -295,6 +320,9 @@ class HostStreamDecoder:
             if err[0, j] or err[1, j]:
                 what, bad = ("luma", err[0, j]) if err[0, j] else ("chroma", err[1, j])
                 raise ValueError(f"frame {i}: malformed packed {what} stream at block {int(bad) - 1}")
+            if self.output == "rgb":
+                consume(i, s.rgb_h[j].numpy())
+                continue
             y = s.y_h[j].numpy()[:hp, :wp]
             u = v = None
             if hdr["chroma"]:
@@ -306,14 +334,17 @@ class HostStreamDecoder:
     def decode_file(self, path: str, consume) -> dict:
         """Decode the container at `path`; consume(i, y, u, v) is called for every frame in order
         with host uint8 arrays cropped to the picture (u, v None for a luma-only file), valid
-        inside the call.  Returns {"frames", "frame_type", "coding", "layout"}.  A malformed file
-        or record raises ValueError after every earlier frame has been delivered; no later frame
-        is delivered."""
+        inside the call.  With output="rgb" it is consume(i, rgb), rgb a host uint8 [h, w, 3]
+        array, and a luma-only file raises ValueError before any frame is queued.  Returns
+        {"frames", "frame_type", "coding", "layout"}.  A malformed file or record raises ValueError
+        after every earlier frame has been delivered; no later frame is delivered."""
         eng = self.eng
         hdr, frames = packedfile.open_frames(path)
         try:
             if (hdr["h"], hdr["w"], hdr["bs"], hdr["nb"]) != (eng.h, eng.w, eng.bs, eng.nb):
                 raise ValueError(f"{path}: {hdr['w']}x{hdr['h']} bs {hdr['bs']} does not match this decoder")
+            if self.output == "rgb" and not hdr["chroma"]:
+                raise ValueError(f"{path}: a luma-only file has no chroma to make RGB from (output=\"rgb\")")
             if hdr["chroma"] and self.fme:
                 raise NotImplementedError("chroma with FMEEnable is not built")
             if hdr["chroma"] and eng.bs != 16:
@@ -383,6 +414,8 @@ class HostStreamDecoder:
     def decode_to_yuv(self, path: str, out_path: str) -> dict:
         """The decoded frames as a planar file, Y | U | V per frame at picture size (Y alone for a
         luma-only file): decoder.save_yuv420's / save_decoded_frames' bytes."""
+        if self.output == "rgb":
+            raise ValueError("decode_to_yuv needs output=\"yuv420\" (this decoder delivers RGB: decode_to_rgb)")
         with open(out_path, "wb") as f:
             def consume(i, y, u, v):
                 f.write(np.ascontiguousarray(y).tobytes())
@@ -390,3 +423,10 @@ class HostStreamDecoder:
                     f.write(np.ascontiguousarray(u).tobytes())
                     f.write(np.ascontiguousarray(v).tobytes())
             return self.decode_file(path, consume)
+
+    def decode_to_rgb(self, path: str, out_path: str) -> dict:
+        """The decoded frames as raw RGB24 at picture size, frame after frame (output="rgb")."""
+        if self.output != "rgb":
+            raise ValueError("decode_to_rgb needs a decoder built with output=\"rgb\"")
+        with open(out_path, "wb") as f:
+            return self.decode_file(path, lambda i, rgb: f.write(rgb.tobytes()))

@@ -19,6 +19,10 @@ are persistent P-runs with the previous chunk's reconstruction as their referenc
 encode_stream() runs several GOPs back to back with two sets of frame / packed buffers: the
 next GOP's upload is queued before the current GOP encodes, so the H2D engine never waits for
 the compute stream (a GOP then costs about its upload time).
+
+With input="rgb" the host hands over 8-bit RGB pictures at picture size instead of padded planes:
+copy stream A uploads a unit's pictures and converts them right behind the copy (so_rgb_to_yuv420)
+into the same device planes, inside the unit's upload event; everything after that is unchanged.
 """
 from __future__ import annotations
 
@@ -35,9 +39,11 @@ from .hwqueue import dedicated_stream
 class _Buffers:
     """One GOP in flight: device frames, packed streams and their pinned host copies."""
 
-    def __init__(self, eng, nframes: int, dev, chroma: bool = False, lengths: bool = False):
+    def __init__(self, eng, nframes: int, dev, chroma: bool = False, lengths: bool = False, rgb_hw=None):
         nb, F = eng.nb, nframes
         self.frames_dev = alloc_planes(F, eng.h, eng.w, dev)
+        # input="rgb": where a unit's pictures land before so_rgb_to_yuv420 writes frames_dev / uv_dev
+        self.rgb_dev = torch.empty((F, *rgb_hw, 3), dtype=torch.uint8, device=dev) if rgb_hw else None
         self.offs = torch.empty((F, nb + 1), dtype=torch.int32, device=dev)
         cap = eng.pack_bound() + (eng.pack_chroma_bound() if chroma else 0)   # a row: luma, then chroma
         self.packed = torch.empty((F, cap), dtype=torch.uint8, device=dev)
@@ -87,10 +93,19 @@ class _PackedViews:
 
 class HostStreamEncoder:
     def __init__(self, codec, nframes: int, chunk: int = 2, nbuf: int = 1, upload: str = "chunk",
-                 lengths: bool = False):
+                 lengths: bool = False, input: str = "yuv420"):
         """upload: "chunk" = one H2D copy per encode unit (the I-frame, each P-run chunk), "frame"
         = one per frame.  lengths: the results also hold each frame's per-block byte counts
-        ("block_bytes", and "chroma_block_bytes" with a chroma=True codec), which write_packed needs."""
+        ("block_bytes", and "chroma_block_bytes" with a chroma=True codec), which write_packed needs.
+        input: "yuv420" = padded Y (and UV) planes from the host; "rgb" (chroma=True codecs) = pinned
+        uint8 [F, h, w, 3] pictures at picture size, no padding on the host: each unit's pictures are
+        uploaded as they are and converted behind the copy on the H2D stream (so_rgb_to_yuv420 with the
+        codec's `colour`) into the same device planes, before the unit's event is recorded."""
+        if input not in ("yuv420", "rgb"):
+            raise ValueError(f"input {input!r} (\"yuv420\" or \"rgb\")")
+        if input == "rgb" and not codec.chroma:
+            raise ValueError("input=\"rgb\" needs a chroma=True codec (RGB for a luma-only codec is not built)")
+        self.input = input
         eng = codec.engine()
         self.codec, self.eng, self.nframes, self.chunk = codec, eng, int(nframes), int(chunk)
         if upload not in ("chunk", "frame"):
@@ -107,7 +122,8 @@ class HostStreamEncoder:
         # like the luma symbols, one set of ChromaSymbols serves every buffer set: the compute
         # stream packs a GOP's symbols before the next GOP's work overwrites them
         self.csyms = [eng.new_chroma_symbols() for _ in range(self.nframes)] if self.chroma else None
-        self.bufs = [_Buffers(eng, self.nframes, self.dev, self.chroma, self.lengths)
+        self.rgb_hw = (int(codec.h_pixels), int(codec.w_pixels)) if input == "rgb" else None
+        self.bufs = [_Buffers(eng, self.nframes, self.dev, self.chroma, self.lengths, self.rgb_hw)
                      for _ in range(max(1, int(nbuf)))]
 
     @property
@@ -115,11 +131,21 @@ class HostStreamEncoder:
         return self.bufs[0].frames_dev
 
     def _check(self, frames_host):
+        if self.input == "rgb":
+            shape = tuple(self.bufs[0].rgb_dev.shape)
+            if (not isinstance(frames_host, torch.Tensor) or frames_host.dtype != torch.uint8
+                    or tuple(frames_host.shape) != shape or not frames_host.is_contiguous() or not frames_host.is_pinned()):
+                raise ValueError(f"input=\"rgb\": frames must be pinned contiguous uint8 {list(shape)} (picture size)")
+            return
         if tuple(frames_host.shape) != tuple(self.bufs[0].frames_dev.shape) or not frames_host.is_pinned():
             raise ValueError("frames_host must be pinned uint8 of the encoder's padded frame shape")
 
     def _check_uv(self, uv_gops, ngops: int) -> list:
         """One pinned uint8 [F, 2, Hp/2, Wp/2] per GOP with a chroma=True codec, none otherwise."""
+        if self.input == "rgb":
+            if uv_gops is not None:
+                raise ValueError("uv planes were given, but input=\"rgb\" makes them from the RGB pictures")
+            return [None] * ngops
         if not self.chroma:
             if uv_gops is not None:
                 raise ValueError("uv planes were given, but the codec was built with chroma=False")
@@ -157,7 +183,12 @@ class HostStreamEncoder:
             if b.enc_done is not None:
                 self.h2d.wait_event(b.enc_done)      # the GOP that last used these frames is encoded
             for k0, k1 in units:
-                b.frames_dev[k0:k1].copy_(frames_host[k0:k1], non_blocking=True)
+                if self.input == "rgb":
+                    b.rgb_dev[k0:k1].copy_(frames_host[k0:k1], non_blocking=True)
+                    self.eng.rgb_to_yuv420(b.rgb_dev[k0:k1], self.codec.colour, out_y=b.frames_dev[k0:k1],
+                                           out_uv=b.uv_dev[k0:k1])
+                else:
+                    b.frames_dev[k0:k1].copy_(frames_host[k0:k1], non_blocking=True)
                 if uv_host is not None:
                     b.uv_dev[k0:k1].copy_(uv_host[k0:k1], non_blocking=True)
                 ev = torch.cuda.Event()
@@ -181,7 +212,8 @@ class HostStreamEncoder:
         return res
 
     def encode(self, frames_host: torch.Tensor, intra_dur: int, uv_host: torch.Tensor | None = None) -> dict:
-        """frames_host: pinned uint8 [F, Hp, Wp].  Returns {"packed": [host uint8 view per
+        """frames_host: pinned uint8 [F, Hp, Wp] (input="rgb": [F, h, w, 3] at picture size, and no
+        uv_host).  Returns {"packed": [host uint8 view per
         frame], "bytes": [...], "sse": host int64 [F], "frame_type": [...]} once everything
         is in host memory (the views stay valid until the next call).
         With a chroma=True codec, uv_host: pinned uint8 [F, 2, Hp/2, Wp/2], padded with 128
