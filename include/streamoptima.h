@@ -690,6 +690,53 @@ int so_yuv420_to_rgb(const uint8_t* const* y, const uint8_t* const* u, const uin
                      size_t pitch, size_t plane_stride, void* stream);
 
 /*
+ * Scaling (build extension; DESIGN.md "Scaling"): a separable polyphase resampler for 8-bit 4:2:0
+ * pictures, exact integers, one launch for Y, U and V of a batch of frames, asynchronous on
+ * `stream`, no host synchronisation.  tests/scaleref.py restates it in numpy.
+ *   tables      one per axis and plane kind (luma horizontal yh, luma vertical yv, chroma horizontal
+ *               ch, chroma vertical cv), each as coef int16 [n_dst][taps], first int32 [n_dst] and
+ *               taps (1..32), in DEVICE memory.  streamoptima_amd.scale.taps builds them: the centre
+ *               of output j is (j + 0.5) n_src / n_dst - 0.5 (cell centres, the siting of the colour
+ *               conversion's chroma), the kernel function (bilinear; Catmull-Rom bicubic, a = -0.5;
+ *               lanczos3) is stretched by max(1, n_src / n_dst), the weights at the integer positions
+ *               strictly inside its support are normalised, multiplied by 16384 and rounded, and the
+ *               largest tap takes what makes the row sum exactly 16384; sum |coef| <= 32768 per row.
+ *               first[j] + t may lie outside the source: the index is clamped (edge replication).
+ *   arithmetic  per plane, >> the arithmetic shift (floor), horizontal first, then vertical:
+ *                 hsum(y, j) = sum_t coef_h[j][t] * src[y][clamp(first_h[j] + t, 0, ws - 1)]
+ *                 mid(y, j)  = clamp((hsum + 128) >> 8, -32768, 32767)      int16, 6 fractional bits
+ *                 vsum(i, j) = sum_t coef_v[i][t] * mid(clamp(first_v[i] + t, 0, hs - 1), j)
+ *                 out(i, j)  = clip((vsum + (1 << 19)) >> 20, 0, 255)
+ *   int32       with tables as above |hsum| <= 255 * 32768 < 2^23, |mid| <= 255 * 2 * 64 = 32640 (the
+ *               int16 clamp never acts), |vsum| <= 32640 * 32768 < 2^30, and 2^19 more stays in int32.
+ *               A constant plane maps to the same constant; n_src == n_dst gives taps = 1, coef =
+ *               16384, first[j] = j, an exact copy.  The final clip does act (ringing on hard edges).
+ *               The tables are not validated: for any contents the kernel stays inside its buffers
+ *               (both clamps above) and sums with wrapping unsigned arithmetic; results are
+ *               specified only for tables built as above.
+ *   source      sy, su, sv: HOST arrays of nframes device pointers to the top-left sample of hs x ws
+ *               luma and hs/2 x ws/2 chroma pictures, rows pitch_y and pitch_c bytes apart (any
+ *               alignment: the picture area of padded planes, or a cropped view).  Only the picture
+ *               area is read.
+ *   destination dy, du, dv: dense Hp x Wp luma planes (pitch Wp) and Hp/2 x Wp/2 chroma planes (pitch
+ *               Wp/2).  The hd x wd picture is written top-left; every other sample of the planes is
+ *               written as 128 by the same launch (the padding so_rgb_to_yuv420 writes).
+ *   luma only   su == sv == du == dv == NULL scales luma alone (the chroma tables are ignored); a
+ *               partial set is invalid.
+ * SO_E_INVALID before any launch, the argument named in so_last_error: a size that is not positive,
+ * or with chroma odd; Hp or Wp smaller than the picture, or with chroma odd; a pitch shorter than a
+ * row; taps outside 1..32; nframes < 0; a NULL pointer or table; a destination that overlaps a source
+ * or another destination.  nframes == 0 with valid scalars returns SO_OK.  SO_E_UNSUPPORTED: a ratio
+ * so extreme that no tile of it fits the LDS (far beyond what 32 taps resample).
+ */
+int so_scale_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const uint8_t* const* sv, int nframes,
+                    int hs, int ws, size_t pitch_y, size_t pitch_c, uint8_t* const* dy, uint8_t* const* du,
+                    uint8_t* const* dv, int hd, int wd, int Hp, int Wp, const int16_t* coef_yh,
+                    const int32_t* first_yh, int taps_yh, const int16_t* coef_yv, const int32_t* first_yv,
+                    int taps_yv, const int16_t* coef_ch, const int32_t* first_ch, int taps_ch,
+                    const int16_t* coef_cv, const int32_t* first_cv, int taps_cv, void* stream);
+
+/*
  * out[i] = sum of rows[i][0..len) (int32 -> int64) for i < n: the per-frame SSE of a GOP from
  * the encode kernels' per-block / per-row out_sse arrays (rows: a HOST array of device
  * pointers), one launch.

@@ -64,6 +64,8 @@ _SIGS = {
     "so_chroma_recon_frame": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "so_rgb_to_yuv420": ([_vp, _i, _i, _i, _i, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "so_yuv420_to_rgb": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _sz, _vp], _i),
+    "so_scale_yuv420": ([_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _i, _i, _i, _i,
+                         _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp], _i),
     "so_block_xform": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "so_encode_p_run_stripe": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_uint32, _i, _vp], _i),

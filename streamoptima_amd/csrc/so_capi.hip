@@ -17,6 +17,7 @@
 #include "so_common.h"
 #include "so_packfmt.h"
 #include "so_run.h"
+#include "so_scale.h"
 
 namespace so {
 
@@ -1339,6 +1340,135 @@ int so_yuv420_to_rgb(const uint8_t* const* y, const uint8_t* const* u, const uin
     SO_TRY(colour_pointers(fn, rgb, y, u, v, nframes));
     SO_TRY(colour_alias(fn, rgb, y, u, v, nframes, g, layout, false));
     return colour_inverse_launch(layout, y, u, v, rgb, nframes, g, (hipStream_t)stream);
+}
+
+// ---- scaling (so_scale.hip) -----------------------------------------------------------------------
+namespace {
+int scale_table(const char* fn, const char* what, const int16_t* coef, const int32_t* first, int taps,
+                ScaleTable* t) {
+    if (taps < 1 || taps > kScaleMaxTaps) {
+        set_error("%s: taps_%s %d outside [1, %d]", fn, what, taps, kScaleMaxTaps);
+        return SO_E_INVALID;
+    }
+    if (!coef || !first) {
+        set_error("%s: %s_%s is NULL", fn, !coef ? "coef" : "first", what);
+        return SO_E_INVALID;
+    }
+    t->coef = coef; t->first = first; t->taps = taps;
+    return SO_OK;
+}
+}  // namespace
+
+int so_scale_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const uint8_t* const* sv, int nframes,
+                    int hs, int ws, size_t pitch_y, size_t pitch_c, uint8_t* const* dy, uint8_t* const* du,
+                    uint8_t* const* dv, int hd, int wd, int Hp, int Wp, const int16_t* coef_yh,
+                    const int32_t* first_yh, int taps_yh, const int16_t* coef_yv, const int32_t* first_yv,
+                    int taps_yv, const int16_t* coef_ch, const int32_t* first_ch, int taps_ch,
+                    const int16_t* coef_cv, const int32_t* first_cv, int taps_cv, void* stream) {
+    const char* fn = "so_scale_yuv420";
+    const int nchroma = (su != nullptr) + (sv != nullptr) + (du != nullptr) + (dv != nullptr);
+    if (nchroma != 0 && nchroma != 4) {
+        set_error("%s: %s is NULL (su, sv, du and dv are all given, or all NULL for luma only)", fn,
+                  !su ? "su" : !sv ? "sv" : !du ? "du" : "dv");
+        return SO_E_INVALID;
+    }
+    const bool chroma = nchroma == 4;
+    if (hs <= 0 || ws <= 0 || (chroma && (hs % 2 || ws % 2))) {
+        set_error("%s: hs %d, ws %d (a source picture is positive%s)", fn, hs, ws,
+                  chroma ? ", and even both ways with chroma" : "");
+        return SO_E_INVALID;
+    }
+    if (hd <= 0 || wd <= 0 || (chroma && (hd % 2 || wd % 2))) {
+        set_error("%s: hd %d, wd %d (a destination picture is positive%s)", fn, hd, wd,
+                  chroma ? ", and even both ways with chroma" : "");
+        return SO_E_INVALID;
+    }
+    if (Hp < hd || Wp < wd || (chroma && (Hp % 2 || Wp % 2))) {
+        set_error("%s: Hp %d, Wp %d (at least the picture's %d x %d%s)", fn, Hp, Wp, hd, wd,
+                  chroma ? ", and even with chroma" : "");
+        return SO_E_INVALID;
+    }
+    if ((long long)Hp * Wp > (1ll << 31) || (long long)hs * ws > (1ll << 31)) {
+        set_error("%s: %d x %d -> %d x %d: frame too large", fn, hs, ws, Hp, Wp);
+        return SO_E_INVALID;
+    }
+    if (pitch_y < (size_t)ws) {
+        set_error("%s: pitch_y %zu below a row's %d bytes", fn, pitch_y, ws);
+        return SO_E_INVALID;
+    }
+    if (chroma && pitch_c < (size_t)(ws / 2)) {
+        set_error("%s: pitch_c %zu below a row's %d bytes", fn, pitch_c, ws / 2);
+        return SO_E_INVALID;
+    }
+    if (nframes < 0) {
+        set_error("%s: nframes %d", fn, nframes);
+        return SO_E_INVALID;
+    }
+    ScaleGeom g{};
+    g.nplanes = chroma ? 3 : 1;
+    g.p[0].hs = hs; g.p[0].ws = ws; g.p[0].hd = hd; g.p[0].wd = wd; g.p[0].Hp = Hp; g.p[0].Wp = Wp;
+    g.p[0].spitch = pitch_y;
+    SO_TRY(scale_table(fn, "yh", coef_yh, first_yh, taps_yh, &g.p[0].h));
+    SO_TRY(scale_table(fn, "yv", coef_yv, first_yv, taps_yv, &g.p[0].v));
+    if (chroma) {
+        g.p[1].hs = hs / 2; g.p[1].ws = ws / 2; g.p[1].hd = hd / 2; g.p[1].wd = wd / 2;
+        g.p[1].Hp = Hp / 2; g.p[1].Wp = Wp / 2;
+        g.p[1].spitch = pitch_c;
+        SO_TRY(scale_table(fn, "ch", coef_ch, first_ch, taps_ch, &g.p[1].h));
+        SO_TRY(scale_table(fn, "cv", coef_cv, first_cv, taps_cv, &g.p[1].v));
+    }
+    if (!scale_tiles(&g)) {
+        set_error("%s: %d x %d -> %d x %d with %d / %d taps: no tile of this ratio fits the LDS", fn, hs, ws, hd,
+                  wd, taps_yh, taps_yv);
+        return SO_E_UNSUPPORTED;
+    }
+    if (nframes == 0) return SO_OK;
+    SO_NEED(sy, fn); SO_NEED(dy, fn);
+
+    // A source is hs rows of ws bytes a pitch apart (taken as one span), a destination a dense plane.
+    // A destination may share no byte with a source or another destination; sources may repeat.
+    const uint8_t* const* srcs[3] = {sy, su, sv};
+    uint8_t* const* dsts[3] = {dy, du, dv};
+    static const char* const sname[3] = {"sy", "su", "sv"};
+    static const char* const dname[3] = {"dy", "du", "dv"};
+    std::vector<ColourSpan> spans;
+    spans.reserve((size_t)nframes * 6);
+    for (int i = 0; i < nframes; ++i)
+        for (int k = 0; k < g.nplanes; ++k) {
+            const ScalePlane& p = g.p[k != 0];
+            if (!srcs[k][i] || !dsts[k][i]) {
+                set_error("%s: %s[%d] is NULL", fn, !srcs[k][i] ? sname[k] : dname[k], i);
+                return SO_E_INVALID;
+            }
+            const uintptr_t ps = reinterpret_cast<uintptr_t>(srcs[k][i]), pd = reinterpret_cast<uintptr_t>(dsts[k][i]);
+            spans.push_back({ps, ps + (size_t)(p.hs - 1) * p.spitch + p.ws, false, sname[k], i});
+            spans.push_back({pd, pd + (size_t)p.Hp * p.Wp, true, dname[k], i});
+        }
+    std::sort(spans.begin(), spans.end(), [](const ColourSpan& a, const ColourSpan& b) { return a.lo < b.lo; });
+    const ColourSpan *far_src = nullptr, *far_dst = nullptr;   // the furthest end so far of each kind
+    for (const ColourSpan& s : spans) {
+        const ColourSpan* hit = far_dst && s.lo < far_dst->hi ? far_dst
+                                : s.dst && far_src && s.lo < far_src->hi ? far_src : nullptr;
+        if (hit) {
+            set_error("%s: %s[%d] aliases %s[%d] (a destination overlaps a source or another destination)", fn,
+                      s.what, s.frame, hit->what, hit->frame);
+            return SO_E_INVALID;
+        }
+        const ColourSpan*& far = s.dst ? far_dst : far_src;
+        if (!far || s.hi > far->hi) far = &s;
+    }
+
+    for (int f0 = 0; f0 < nframes; f0 += kScaleBatch) {
+        const int m = nframes - f0 < kScaleBatch ? nframes - f0 : kScaleBatch;
+        ScalePtrs p{};
+        for (int i = 0; i < m; ++i)
+            for (int k = 0; k < g.nplanes; ++k) {
+                p.s[k][i] = srcs[k][f0 + i];
+                p.d[k][i] = dsts[k][f0 + i];
+            }
+        SO_TRY(scale_launch(p, m, g, (hipStream_t)stream));
+    }
+    return SO_OK;
 }
 
 // ---- chroma 4:2:0 (so_chroma.hip) ----------------------------------------------------------------

@@ -306,7 +306,8 @@ class decoder:
         return host
 
     def decode_packed_stream(self, path: str, out_path: str | None = None, consume=None, chunk: int = 2,
-                             nbuf: int = 2, output: str = "yuv420", colour=None) -> dict:
+                             nbuf: int = 2, output: str = "yuv420", colour=None, output_size=None,
+                             scale: str = "lanczos3") -> dict:
         """decode_packed_file's frames without its footprint (hostdecode.HostStreamDecoder): the file
         is read as it goes, P-frames and chroma are decoded from the packed records straight to
         pixels (so_decode_p_frames, so_decode_chroma_frames), and upload, decode and download overlap
@@ -316,24 +317,31 @@ class decoder:
         cropped to the picture, valid inside the call.  One of the two.  output="rgb" (with `colour`,
         a colour.Colour; None: BT.601, full range) converts every frame on the device: the file is
         then raw RGB24 and the call consume(i, rgb) with rgb [h, w, 3]; a luma-only file raises
-        ValueError.  The stream decoder is kept with this instance.  Returns {"frames",
+        ValueError.  output_size=(ho, wo) resamples every frame on the device to that size (`scale`:
+        "bilinear", "bicubic" or "lanczos3") before it is converted or downloaded; the frames, the
+        file and the arrays consume receives then have that size.  The stream decoder is kept with
+        this instance.  Returns {"frames",
         "frame_type", "coding", "layout"}."""
         from .colour import as_colour
         from .hostdecode import HostStreamDecoder
         if (out_path is None) == (consume is None):
             raise ValueError("decode_packed_stream: give out_path or consume")
-        key = (int(chunk), int(nbuf), output, as_colour(colour))
+        key = (int(chunk), int(nbuf), output, as_colour(colour), None if output_size is None else tuple(output_size),
+               scale)
         if getattr(self, "_stream_dec", None) is None or self._stream_dec[0] != key:
-            self._stream_dec = (key, HostStreamDecoder(self, chunk=chunk, nbuf=nbuf, output=output, colour=colour))
+            self._stream_dec = (key, HostStreamDecoder(self, chunk=chunk, nbuf=nbuf, output=output, colour=colour,
+                                                       output_size=output_size, scale=scale))
         hs = self._stream_dec[1]
         if out_path is None:
             return hs.decode_file(path, consume)
         return hs.decode_to_rgb(path, out_path) if output == "rgb" else hs.decode_to_yuv(path, out_path)
 
-    def decode_to_rgb(self, path: str, out_path: str, colour=None, chunk: int = 2, nbuf: int = 2) -> dict:
-        """The packed file at `path` as raw RGB24 at picture size, frame after frame:
-        decode_packed_stream with output="rgb"."""
-        return self.decode_packed_stream(path, out_path=out_path, chunk=chunk, nbuf=nbuf, output="rgb", colour=colour)
+    def decode_to_rgb(self, path: str, out_path: str, colour=None, chunk: int = 2, nbuf: int = 2, output_size=None,
+                      scale: str = "lanczos3") -> dict:
+        """The packed file at `path` as raw RGB24 at picture size (or at output_size), frame after
+        frame: decode_packed_stream with output="rgb"."""
+        return self.decode_packed_stream(path, out_path=out_path, chunk=chunk, nbuf=nbuf, output="rgb", colour=colour,
+                                         output_size=output_size, scale=scale)
 
     def save_decoded_frames(self, filename="yuv/decoded_bitstream_frames.yuv"):
         if not self.decoded_vid_f:

@@ -890,19 +890,21 @@ class Engine:
 
     # ---- colour conversion (so_colour.hip) ---------------------------------------------------
     def rgb_to_yuv420(self, rgb: torch.Tensor, colour=None, layout: str = "hwc", out_y: torch.Tensor | None = None,
-                      out_uv: torch.Tensor | None = None):
+                      out_uv: torch.Tensor | None = None, plane_hw=None):
         """8-bit RGB pictures -> (y [F, Hp, Wp], uv [F, 2, Hp/2, Wp/2]): the engine's padded planes
         in alloc_planes layout, every sample outside the picture 128, one so_rgb_to_yuv420 launch on
         the current stream, no host synchronisation.  rgb: uint8 [F, h, w, 3] ("hwc") or
         [F, 3, h, w] ("chw") on the device, h and w even and at most the engine's size; a cropped
         view of a larger picture converts in place (colour.rgb_pointers).  colour: a colour.Colour
-        (None: BT.601, full range).  out_y / out_uv: planes to write, of exactly those shapes."""
+        (None: BT.601, full range).  out_y / out_uv: planes to write, of exactly those shapes.
+        plane_hw: (Hp, Wp) of the planes when they are not the engine's (even; the picture's own size
+        for planes without padding)."""
         from . import colour as _colour
         col = _colour.as_colour(colour)
         ptrs, n, h, w, pitch, plane = _colour.rgb_pointers(rgb, layout, self.device)
-        hp, wp = self.h, self.w
+        hp, wp = (int(plane_hw[0]), int(plane_hw[1])) if plane_hw else (self.h, self.w)
         if h % 2 or w % 2 or h > hp or w > wp:
-            raise ValueError(f"rgb_to_yuv420: a {w}x{h} picture (even, at most the engine's {wp}x{hp})")
+            raise ValueError(f"rgb_to_yuv420: a {w}x{h} picture (even, at most the planes' {wp}x{hp})")
         if out_y is None:
             out_y = alloc_planes(n, hp, wp, self.device)
         if out_uv is None:
@@ -916,17 +918,18 @@ class Engine:
         return out_y, out_uv
 
     def yuv420_to_rgb(self, y, uv, h: int, w: int, colour=None, layout: str = "hwc",
-                      out: torch.Tensor | None = None) -> torch.Tensor:
+                      out: torch.Tensor | None = None, plane_hw=None) -> torch.Tensor:
         """The inverse: the h x w picture area of padded planes -> uint8 [F, h, w, 3] ("hwc") or
         [F, 3, h, w] ("chw"), one so_yuv420_to_rgb launch on the current stream.  y: [F, Hp, Wp] or
         a sequence of [Hp, Wp] planes; uv: [F, 2, Hp/2, Wp/2] or a sequence of (u, v) plane pairs
-        (Hp, Wp: the engine's size).  out: a tensor or view of the result's shape to write into."""
+        (Hp, Wp: the engine's size, or plane_hw when given).  out: a tensor or view of the result's shape
+        to write into."""
         from . import colour as _colour
         col = _colour.as_colour(colour)
-        hp, wp = self.h, self.w
+        hp, wp = (int(plane_hw[0]), int(plane_hw[1])) if plane_hw else (self.h, self.w)
         h, w = int(h), int(w)
         if h <= 0 or w <= 0 or h % 2 or w % 2 or h > hp or w > wp:
-            raise ValueError(f"yuv420_to_rgb: a {w}x{h} picture (even, at most the engine's {wp}x{hp})")
+            raise ValueError(f"yuv420_to_rgb: a {w}x{h} picture (even, at most the planes' {wp}x{hp})")
         ys, uvs = list(y), list(uv)
         n = len(ys)
         if len(uvs) != n:
@@ -943,6 +946,56 @@ class Engine:
                                        _colour.layout_code(layout), ptrs, pitch, plane, _lib.stream_handle(self.device))
         _lib.check(rc, "so_yuv420_to_rgb")
         return out
+
+    # ---- scaling (so_scale.hip) --------------------------------------------------------------
+    def scale_yuv420(self, y, uv, plan, src_hw=None, out_y: torch.Tensor | None = None,
+                     out_uv: torch.Tensor | None = None, out_hw=None):
+        """Resample 4:2:0 pictures with a scale.ScalePlan: one so_scale_yuv420 launch on the current
+        stream, no host synchronisation.  y: [F, H, W] or a sequence of planes or views with
+        contiguous rows; uv: [F, 2, H/2, W/2] or a sequence of (u, v) pairs, None for luma only.
+        src_hw: the picture area read from the top-left of every plane (default: the whole plane);
+        it must be plan.src_hw.  Returns (y [F, Hp, Wp], uv [F, 2, Hp/2, Wp/2] or None) with the
+        plan.dst_hw picture top-left and 128 elsewhere: Hp x Wp is the engine's padded size in
+        alloc_planes layout, or out_hw when given (plan.dst_hw itself for planes without padding).
+        out_y / out_uv: planes of exactly those shapes to write."""
+        from . import scale as _scale
+        if not isinstance(plan, _scale.ScalePlan):
+            raise ValueError(f"scale_yuv420: plan must be a streamoptima_amd.scale.ScalePlan, got {type(plan).__name__}")
+        chroma = uv is not None
+        if chroma and not plan.chroma:
+            raise ValueError("scale_yuv420: the plan was built without chroma tables")
+        ys = list(y)
+        n = len(ys)
+        hs, ws = _scale.check_size(src_hw if src_hw is not None else tuple(ys[0].shape[-2:]) if n else plan.src_hw,
+                                   "scale_yuv420 src_hw", chroma)
+        if (hs, ws) != plan.src_hw:
+            raise ValueError(f"scale_yuv420: a {ws}x{hs} source, the plan takes {plan.src_hw[1]}x{plan.src_hw[0]}")
+        hd, wd = plan.dst_hw
+        hp, wp = _scale.check_size(out_hw, "scale_yuv420 out_hw", chroma) if out_hw is not None else (self.h, self.w)
+        if hd > hp or wd > wp:
+            raise ValueError(f"scale_yuv420: a {wd}x{hd} picture does not fit the {wp}x{hp} planes")
+        psy, _, pitch_y = _scale.plane_views(ys, n, (hs, ws), self.device, "scale_yuv420 y")
+        psu = psv = pdu = pdv = None
+        pitch_c = 0
+        if chroma:
+            uvs = list(uv)
+            psu, _, pitch_c = _scale.plane_views([t[0] for t in uvs], n, (hs // 2, ws // 2), self.device, "scale_yuv420 uv")
+            psv, _, pitch_v = _scale.plane_views([t[1] for t in uvs], n, (hs // 2, ws // 2), self.device, "scale_yuv420 uv")
+            if n and pitch_v != pitch_c:
+                raise ValueError(f"scale_yuv420 uv: the planes of one call share a row pitch ({pitch_c} and {pitch_v})")
+        from . import colour as _colour
+        if out_y is None:
+            out_y = alloc_planes(n, hp, wp, self.device)
+        pdy = _colour.plane_pointers(out_y, n, (hp, wp), self.device, "scale_yuv420 out_y")
+        if chroma:
+            if out_uv is None:
+                out_uv = alloc_planes(2 * n, hp // 2, wp // 2, self.device).view(n, 2, hp // 2, wp // 2)
+            pdu = _colour.plane_pointers([t[0] for t in out_uv], n, (hp // 2, wp // 2), self.device, "scale_yuv420 out_uv")
+            pdv = _colour.plane_pointers([t[1] for t in out_uv], n, (hp // 2, wp // 2), self.device, "scale_yuv420 out_uv")
+        rc = self.lib.so_scale_yuv420(psy, psu, psv, n, hs, ws, pitch_y, pitch_c, pdy, pdu, pdv, hd, wd, hp, wp,
+                                      *plan.table_args(), _lib.stream_handle(self.device))
+        _lib.check(rc, "so_scale_yuv420")
+        return out_y, (out_uv if chroma else None)
 
     def sse_into(self, a: torch.Tensor, b: torch.Tensor, acc: torch.Tensor) -> None:
         """acc (uint64 view of an int64 device scalar) += sum((a-b)^2)."""

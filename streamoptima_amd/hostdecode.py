@@ -22,6 +22,9 @@ so_inter_recon_ex).
 With output="rgb" the compute stream ends a unit by converting its planes (so_yuv420_to_rgb) and
 copy stream B brings down one [chunk, h, w, 3] buffer in place of the Y, U and V planes.
 
+With output_size the compute stream first resamples the picture area of the unit's planes
+(so_scale_yuv420) into planes of exactly that size; those are what is converted or downloaded.
+
 Reconstructions live in a ring of planes: a plane is written again only after its download
 event (the compute stream waits for it) and, by stream order, after its last use as a reference.
 """
@@ -53,11 +56,21 @@ class _Set:
         self.offs = torch.zeros((c, eng.nb + 1), dtype=torch.int32, device=dev)     # [:, 0] stays 0
         self.coffs = torch.zeros((c, eng.nb + 1), dtype=torch.int32, device=dev)
         self.err = torch.zeros((2, c), dtype=torch.int32, device=dev)               # luma row, chroma row
+        self.sy_d = self.suv_d = None
+        if hs.out_hw:
+            # the unit's planes at output size, resampled on the compute stream
+            ho, wo = hs.out_hw
+            self.sy_d = torch.empty((c, ho, wo), dtype=torch.uint8, device=dev)
+            if hs.scale_plan.chroma:
+                self.suv_d = torch.empty((c, 2, ho // 2, wo // 2), dtype=torch.uint8, device=dev)
         if hs.output == "rgb":
             # the unit's pictures, converted on the compute stream, and their one host copy
-            hp, wp = int(hs.dec.h_pixels), int(hs.dec.w_pixels)
+            hp, wp = hs.out_hw or (int(hs.dec.h_pixels), int(hs.dec.w_pixels))
             self.rgb_d = torch.empty((c, hp, wp, 3), dtype=torch.uint8, device=dev)
             self.rgb_h = pinned_empty((c, hp, wp, 3))
+        elif hs.out_hw:
+            self.y_h = pinned_empty(tuple(self.sy_d.shape))
+            self.uv_h = pinned_empty(tuple(self.suv_d.shape)) if self.suv_d is not None else None
         else:
             self.y_h = pinned_empty((c, eng.h, eng.w))
             self.uv_h = pinned_empty((c, 2, eng.h // 2, eng.w // 2)) if hs.chroma_ok else None
@@ -66,20 +79,34 @@ class _Set:
 
 
 class HostStreamDecoder:
-    def __init__(self, dec, chunk: int = 2, nbuf: int = 2, fused: bool = True, output: str = "yuv420", colour=None):
+    def __init__(self, dec, chunk: int = 2, nbuf: int = 2, fused: bool = True, output: str = "yuv420", colour=None,
+                 output_size=None, scale: str = "lanczos3"):
         """dec: a `decoder` (its geometry, Qp, nRefFrames, RCFlag, FMEEnable).  chunk: P-frames
         per unit; nbuf: units in flight.  fused=False decodes P-frames and chroma with the unpack
         and reconstruction kernels on the one dense symbol set instead of the fused kernels (the
         same frames; tools/decode_time.py compares the two).  output: "yuv420" = Y, U and V planes
         to the host; "rgb" = each unit's planes converted on the compute stream (so_yuv420_to_rgb
         with `colour`, a colour.Colour; None: BT.601, full range) and one [chunk, h, w, 3] buffer
-        downloaded in their place.  Every device and page-locked buffer is allocated here."""
+        downloaded in their place.  output_size: (ho, wo) = the compute stream ends a unit by resampling
+        the picture area of its planes to that size (so_scale_yuv420 with the `scale` filter:
+        "bilinear", "bicubic" or "lanczos3") into planes of exactly that size, which are then converted
+        (output="rgb": scale, then convert) or downloaded; a luma-only file scales luma alone.  None:
+        nothing is staged and nothing resampled.  Every device and page-locked buffer is allocated here."""
         if output not in ("yuv420", "rgb"):
             raise ValueError(f"output {output!r} (\"yuv420\" or \"rgb\")")
         self.output, self.colour = output, as_colour(colour)
         if output == "rgb" and (dec.h_pixels % 2 or dec.w_pixels % 2):
             raise ValueError(f"output=\"rgb\" needs an even picture size, got {dec.w_pixels}x{dec.h_pixels}")
         self.fused = bool(fused)
+        self.out_hw = self.scale_plan = None
+        if output_size is not None:
+            from . import scale as _scale
+            # chroma is resampled when this geometry can carry it; refusals before a buffer is allocated
+            chroma = (int(dec.block_size) == 16 and not dec.FMEEnable and dec.h_pixels % 2 == 0 and dec.w_pixels % 2 == 0)
+            plan = ((int(dec.h_pixels), int(dec.w_pixels)), _scale.check_size(output_size, "output_size", chroma),
+                    _scale.check_filter(scale))
+            _scale.ScalePlan.check(*plan, chroma=chroma)
+            self.out_hw = plan[1]
         eng = dec._eng()
         self.dec, self.eng, self.dev = dec, eng, eng.device
         self.chunk, self.nbuf = max(1, int(chunk)), max(1, int(nbuf))
@@ -105,6 +132,8 @@ class HostStreamDecoder:
         self.h2d = dedicated_stream(self.dev, "hoststream.h2d")
         self.d2h = dedicated_stream(self.dev, "hoststream.d2h")
         self.comp = dedicated_stream(self.dev, "hoststream.compute")
+        if self.out_hw:
+            self.scale_plan = _scale.ScalePlan(*plan, chroma=chroma, device=self.dev)
         self.sets = [_Set(self, self.dev) for _ in range(self.nbuf)]
         self.err_h = pinned_empty((self.nbuf, 2, c), torch.int32)        # one slab for every set's words
         self.tmp32 = torch.empty(nb, dtype=torch.int32, device=self.dev)
@@ -268,7 +297,14 @@ class HostStreamDecoder:
                                          rows, maps, coding=coding, out_u=cu, out_v=cv, err=s.err[1])
                 state["refs_u"] = (state["refs_u"] + cu)[-self.nref:]
                 state["refs_v"] = (state["refs_v"] + cv)[-self.nref:]
-            if self.output == "rgb":
+            if self.out_hw:
+                eng.scale_yuv420(outs, [self.cplanes[p] for p in ps] if chroma else None, self.scale_plan,
+                                 src_hw=self.scale_plan.src_hw, out_y=s.sy_d[:n],
+                                 out_uv=s.suv_d[:n] if chroma else None, out_hw=self.out_hw)
+                if self.output == "rgb":
+                    eng.yuv420_to_rgb(s.sy_d[:n], s.suv_d[:n], *self.out_hw, self.colour, out=s.rgb_d[:n],
+                                      plane_hw=self.out_hw)
+            elif self.output == "rgb":
                 eng.yuv420_to_rgb(outs, [self.cplanes[p] for p in ps], self.dec.h_pixels, self.dec.w_pixels,
                                   self.colour, out=s.rgb_d[:n])
             done = torch.cuda.Event()
@@ -277,6 +313,10 @@ class HostStreamDecoder:
             self.d2h.wait_event(done)
             if self.output == "rgb":
                 s.rgb_h[:n].copy_(s.rgb_d[:n], non_blocking=True)
+            elif self.out_hw:
+                s.y_h[:n].copy_(s.sy_d[:n], non_blocking=True)
+                if chroma:
+                    s.uv_h[:n].copy_(s.suv_d[:n], non_blocking=True)
             else:
                 for j, p in enumerate(ps):
                     s.y_h[j].copy_(self.planes[p], non_blocking=True)
@@ -313,7 +353,7 @@ class HostStreamDecoder:
         """Wait for the unit in set s and hand its frames on, in order; a malformed record raises
         once the frames before it are delivered."""
         s.down.synchronize()
-        hp, wp = self.dec.h_pixels, self.dec.w_pixels
+        hp, wp = self.out_hw or (self.dec.h_pixels, self.dec.w_pixels)
         err = self.err_h[k].numpy()
         unit, s.frames = s.frames, []
         for j, (i, _, _, _, _, _) in enumerate(unit):

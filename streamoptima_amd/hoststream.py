@@ -23,6 +23,11 @@ the compute stream (a GOP then costs about its upload time).
 With input="rgb" the host hands over 8-bit RGB pictures at picture size instead of padded planes:
 copy stream A uploads a unit's pictures and converts them right behind the copy (so_rgb_to_yuv420)
 into the same device planes, inside the unit's upload event; everything after that is unchanged.
+
+With source_size=(hs, ws) the host hands over pictures of another size than the one that is coded:
+a unit's planes (or RGB pictures, converted at source size) land in staging planes of that size and
+copy stream A resamples them (so_scale_yuv420) into the same device planes, again inside the unit's
+upload event.
 """
 from __future__ import annotations
 
@@ -39,9 +44,16 @@ from .hwqueue import dedicated_stream
 class _Buffers:
     """One GOP in flight: device frames, packed streams and their pinned host copies."""
 
-    def __init__(self, eng, nframes: int, dev, chroma: bool = False, lengths: bool = False, rgb_hw=None):
+    def __init__(self, eng, nframes: int, dev, chroma: bool = False, lengths: bool = False, rgb_hw=None,
+                 src_hw=None):
         nb, F = eng.nb, nframes
         self.frames_dev = alloc_planes(F, eng.h, eng.w, dev)
+        # source_size: where a unit's planes land at source size before so_scale_yuv420 writes frames_dev / uv_dev
+        self.src_y = self.src_uv = None
+        if src_hw:
+            self.src_y = torch.empty((F, *src_hw), dtype=torch.uint8, device=dev)
+            if chroma:
+                self.src_uv = torch.empty((F, 2, src_hw[0] // 2, src_hw[1] // 2), dtype=torch.uint8, device=dev)
         # input="rgb": where a unit's pictures land before so_rgb_to_yuv420 writes frames_dev / uv_dev
         self.rgb_dev = torch.empty((F, *rgb_hw, 3), dtype=torch.uint8, device=dev) if rgb_hw else None
         self.offs = torch.empty((F, nb + 1), dtype=torch.int32, device=dev)
@@ -93,19 +105,32 @@ class _PackedViews:
 
 class HostStreamEncoder:
     def __init__(self, codec, nframes: int, chunk: int = 2, nbuf: int = 1, upload: str = "chunk",
-                 lengths: bool = False, input: str = "yuv420"):
+                 lengths: bool = False, input: str = "yuv420", source_size=None, scale: str = "lanczos3"):
         """upload: "chunk" = one H2D copy per encode unit (the I-frame, each P-run chunk), "frame"
         = one per frame.  lengths: the results also hold each frame's per-block byte counts
         ("block_bytes", and "chroma_block_bytes" with a chroma=True codec), which write_packed needs.
         input: "yuv420" = padded Y (and UV) planes from the host; "rgb" (chroma=True codecs) = pinned
         uint8 [F, h, w, 3] pictures at picture size, no padding on the host: each unit's pictures are
         uploaded as they are and converted behind the copy on the H2D stream (so_rgb_to_yuv420 with the
-        codec's `colour`) into the same device planes, before the unit's event is recorded."""
+        codec's `colour`) into the same device planes, before the unit's event is recorded.
+        source_size: (hs, ws) = the host's pictures have this size, not the coded one: unpadded pinned
+        uint8 [F, hs, ws] planes (with a chroma=True codec uv [F, 2, hs/2, ws/2]) or [F, hs, ws, 3] RGB
+        pictures, uploaded into staging planes per buffer set and resampled behind the copy on the H2D
+        stream (so_scale_yuv420 with the `scale` filter: "bilinear", "bicubic" or "lanczos3") to the
+        codec's h_pixels x w_pixels, padded with 128.  None: nothing is staged and nothing resampled."""
         if input not in ("yuv420", "rgb"):
             raise ValueError(f"input {input!r} (\"yuv420\" or \"rgb\")")
         if input == "rgb" and not codec.chroma:
             raise ValueError("input=\"rgb\" needs a chroma=True codec (RGB for a luma-only codec is not built)")
         self.input = input
+        self.scale_plan = host_plan = None
+        if source_size is not None:
+            from . import scale as _scale
+            # every refusal (sizes, filter, a ratio beyond the tap bound) before a buffer is allocated
+            host_plan = (_scale.check_size(source_size, "source_size", bool(codec.chroma)),
+                         _scale.check_size((codec.h_pixels, codec.w_pixels), "the coded picture", bool(codec.chroma)),
+                         _scale.check_filter(scale))
+            _scale.ScalePlan.check(*host_plan, chroma=bool(codec.chroma))
         eng = codec.engine()
         self.codec, self.eng, self.nframes, self.chunk = codec, eng, int(nframes), int(chunk)
         if upload not in ("chunk", "frame"):
@@ -122,8 +147,11 @@ class HostStreamEncoder:
         # like the luma symbols, one set of ChromaSymbols serves every buffer set: the compute
         # stream packs a GOP's symbols before the next GOP's work overwrites them
         self.csyms = [eng.new_chroma_symbols() for _ in range(self.nframes)] if self.chroma else None
-        self.rgb_hw = (int(codec.h_pixels), int(codec.w_pixels)) if input == "rgb" else None
-        self.bufs = [_Buffers(eng, self.nframes, self.dev, self.chroma, self.lengths, self.rgb_hw)
+        self.src_hw = host_plan[0] if host_plan else None
+        self.rgb_hw = (self.src_hw or (int(codec.h_pixels), int(codec.w_pixels))) if input == "rgb" else None
+        if host_plan:
+            self.scale_plan = _scale.ScalePlan(*host_plan, chroma=self.chroma, device=self.dev)
+        self.bufs = [_Buffers(eng, self.nframes, self.dev, self.chroma, self.lengths, self.rgb_hw, self.src_hw)
                      for _ in range(max(1, int(nbuf)))]
 
     @property
@@ -136,6 +164,12 @@ class HostStreamEncoder:
             if (not isinstance(frames_host, torch.Tensor) or frames_host.dtype != torch.uint8
                     or tuple(frames_host.shape) != shape or not frames_host.is_contiguous() or not frames_host.is_pinned()):
                 raise ValueError(f"input=\"rgb\": frames must be pinned contiguous uint8 {list(shape)} (picture size)")
+            return
+        if self.src_hw:
+            shape = tuple(self.bufs[0].src_y.shape)
+            if (not isinstance(frames_host, torch.Tensor) or frames_host.dtype != torch.uint8
+                    or tuple(frames_host.shape) != shape or not frames_host.is_contiguous() or not frames_host.is_pinned()):
+                raise ValueError(f"source_size: frames must be pinned contiguous uint8 {list(shape)} (source size, unpadded)")
             return
         if tuple(frames_host.shape) != tuple(self.bufs[0].frames_dev.shape) or not frames_host.is_pinned():
             raise ValueError("frames_host must be pinned uint8 of the encoder's padded frame shape")
@@ -150,13 +184,14 @@ class HostStreamEncoder:
             if uv_gops is not None:
                 raise ValueError("uv planes were given, but the codec was built with chroma=False")
             return [None] * ngops
-        shape = tuple(self.bufs[0].uv_dev.shape)
+        shape = tuple((self.bufs[0].src_uv if self.src_hw else self.bufs[0].uv_dev).shape)
         if uv_gops is None or len(uv_gops) != ngops:
             raise ValueError(f"a chroma=True codec needs uv planes: one pinned uint8 {list(shape)} tensor per GOP")
         for uv in uv_gops:
             if (not isinstance(uv, torch.Tensor) or uv.dtype != torch.uint8 or tuple(uv.shape) != shape
                     or not uv.is_contiguous() or not uv.is_pinned()):
-                raise ValueError(f"uv planes must be pinned contiguous uint8 {list(shape)} (padded with 128)")
+                raise ValueError(f"uv planes must be pinned contiguous uint8 {list(shape)} "
+                                 f"({'source size, unpadded' if self.src_hw else 'padded with 128'})")
         return list(uv_gops)
 
     def _units(self, intra_dur: int) -> list:
@@ -183,14 +218,19 @@ class HostStreamEncoder:
             if b.enc_done is not None:
                 self.h2d.wait_event(b.enc_done)      # the GOP that last used these frames is encoded
             for k0, k1 in units:
+                # with source_size the unit lands in the staging planes and is resampled below
+                y_to, uv_to = (b.src_y, b.src_uv) if self.src_hw else (b.frames_dev, getattr(b, "uv_dev", None))
                 if self.input == "rgb":
                     b.rgb_dev[k0:k1].copy_(frames_host[k0:k1], non_blocking=True)
-                    self.eng.rgb_to_yuv420(b.rgb_dev[k0:k1], self.codec.colour, out_y=b.frames_dev[k0:k1],
-                                           out_uv=b.uv_dev[k0:k1])
+                    self.eng.rgb_to_yuv420(b.rgb_dev[k0:k1], self.codec.colour, out_y=y_to[k0:k1],
+                                           out_uv=uv_to[k0:k1], plane_hw=self.src_hw)
                 else:
-                    b.frames_dev[k0:k1].copy_(frames_host[k0:k1], non_blocking=True)
+                    y_to[k0:k1].copy_(frames_host[k0:k1], non_blocking=True)
                 if uv_host is not None:
-                    b.uv_dev[k0:k1].copy_(uv_host[k0:k1], non_blocking=True)
+                    uv_to[k0:k1].copy_(uv_host[k0:k1], non_blocking=True)
+                if self.src_hw:
+                    self.eng.scale_yuv420(y_to[k0:k1], uv_to[k0:k1] if self.chroma else None, self.scale_plan,
+                                          out_y=b.frames_dev[k0:k1], out_uv=b.uv_dev[k0:k1] if self.chroma else None)
                 ev = torch.cuda.Event()
                 ev.record(self.h2d)
                 up[k0:k1] = [ev] * (k1 - k0)
