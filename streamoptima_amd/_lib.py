@@ -200,9 +200,17 @@ def ptr(t) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def ptr_array(ts) -> ctypes.Array:
+    """A host array of the tensors' device addresses, None giving NULL (never of length 0)."""
+    return (ctypes.c_void_p * max(len(ts), 1))(*[ptr(t) for t in ts])
+
+
+def i32_array(values) -> ctypes.Array:
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
 def ref_array(refs) -> ctypes.Array:
-    arr = (ctypes.c_void_p * len(refs))(*[r.data_ptr() for r in refs])
-    return arr
+    return ptr_array(refs)
 
 
 def stream_handle(device=None) -> int:

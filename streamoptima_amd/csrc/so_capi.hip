@@ -15,6 +15,7 @@
 #include "so_chroma.h"
 #include "so_colour.h"
 #include "so_common.h"
+#include "so_launch.h"
 #include "so_packfmt.h"
 #include "so_run.h"
 #include "so_scale.h"
@@ -38,30 +39,6 @@ int option(int id) {
     return (id > 0 && id < 9) ? g_opt[id].load(std::memory_order_relaxed) : 0;
 }
 
-int me_launch(const uint8_t* cur, const RefSet& refs, int nref, int H, int W, int bs, int sr, int by0, int by1,
-              int32_t* out_best, int32_t* out_sub, hipStream_t st);
-int me_generic_launch(const uint8_t* cur, const RefSet& refs, const uint8_t* planes, size_t pstride, int nref, int H,
-                      int W, int bs, int sr, int by0, int by1, int32_t* out_best, int32_t* out_sub, hipStream_t st);
-int me_fme_launch(const uint8_t* cur, const uint8_t* planes, size_t pstride, int nref, int H, int W, int by0, int by1,
-                  int32_t* out_best, int32_t* out_sub, hipStream_t st);
-int fme_planes_launch(const uint8_t* ref, int H, int W, int wrap, uint8_t* out, size_t pstride, hipStream_t st);
-int me_fastpred_launch(const uint8_t* cur, const uint8_t* const* ptrs, int nptr, int nref, int H, int W, int bs,
-                       int fme, int by0, int by1, int serial, int32_t* out_best, int32_t* out_sub, int32_t* seg_ws,
-                       hipStream_t st);
-constexpr size_t kFastSegWords = 2 * 4096 * 6;   // so_fastme.hip: the speculated chain's segment records
-int p_tile_launch(const uint8_t* cur, const RefSet& refs, int H, int W, int by0, int by1, int qp_rd,
-                  const int32_t* qp_row, const int32_t* qp_map, int32_t* out_best, uint8_t* out_split,
-                  int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae, uint8_t* out_recon,
-                  int32_t* out_sse, hipStream_t st, bool tokens_only = false, const int16_t* prev_mv = nullptr);
-
-int stripe_halo_push_launch(const uint8_t* plane, int W, int by0, int by1, uint8_t* up, uint8_t* dn,
-                            uint32_t* up_flags, uint32_t* dn_flags, int gf, uint32_t epoch, hipStream_t st);
-int frame_push_launch(const uint8_t* plane, int H, int W, uint8_t* dst, uint32_t* flags, uint32_t epoch,
-                      hipStream_t st);
-size_t ssim_tiles(int H, int W, int win);   // so_ssim.hip
-int ssim_launch(const uint8_t* const* a, const uint8_t* const* b, int nframes, int H, int W, size_t pitch_a,
-                size_t pitch_b, int win, double* out, double* ws, hipStream_t st);
-
 #ifdef SO_AB
 // A/B builds only (not in the header): tools that set the SO_AB environment knobs
 // (tools/ab_guard.py) check for this symbol, so a knob can never silently measure the default path
@@ -82,27 +59,6 @@ static bool use_fused(int bs, int sr, int vbs, int nref) {
     return true;
 #endif
 }
-
-int inter_tq_launch(const uint8_t* cur, const RefSet& refs, const uint8_t* planes, size_t pstride, int H, int W,
-                    int bs, int by0, int by1, const int32_t* best, const int32_t* sub, int qp_rd, const int32_t* qp_row,
-                    const int32_t* qp_map, int vbs, double lam, uint8_t* out_split, int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens,
-                    int32_t* out_mae, uint8_t* out_recon, int32_t* out_sse, hipStream_t st);
-int inter_tq_2pass_launch(const uint8_t* cur, const RefSet& refs, int H, int W, const int32_t* best, const int32_t* t1,
-                          int qp_rd, const int32_t* qp_row, const int32_t* roi, int qp_lo, int qp_hi,
-                          int32_t* out_qpmap, uint8_t* out_split, int16_t* out_mv, int16_t* out_qtc,
-                          int32_t* out_tokens, int32_t* out_mae, uint8_t* out_recon, int32_t* out_sse,
-                          hipStream_t st);
-int inter_recon_launch(const RefSet& refs, const uint8_t* planes, size_t pstride, int H, int W, int bs, int qp,
-                       const int32_t* qp_row, const int32_t* qp_map, const uint8_t* split, const int16_t* mv, const int16_t* qtc,
-                       uint8_t* out_recon, hipStream_t st);
-int intra_encode_launch(const uint8_t* cur, int H, int W, int bs, int sr, int by0, int by1, int qp_rd,
-                        const int32_t* qp_row, const int32_t* qp_map, int vbs, double lam, uint8_t* out_split, int16_t* out_mv,
-                        int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae, uint8_t* out_recon,
-                        int32_t* out_sse, uint8_t* idres, hipStream_t st);
-int intra_recon_launch(int H, int W, int bs, int sr, int qp, const int32_t* qp_row, const int32_t* qp_map,
-                       const uint8_t* split,
-                       const int16_t* mv, const int16_t* qtc, uint8_t* out_recon, uint8_t* idres,
-                       hipStream_t st);
 
 // ---- validation ------------------------------------------------------------------------------
 // VBSEnable flag and calculate_RD_cost's lambda (Encoder.py:1133-1158)
@@ -184,124 +140,123 @@ static int make_refs(const char* fn, const uint8_t* const* refs, int nref, RefSe
     return SO_OK;
 }
 
-#define SO_TRY(x)                 \
-    do {                          \
-        int _rc = (x);            \
-        if (_rc != SO_OK) return _rc; \
-    } while (0)
+// after make_refs: the reconstruction may be none of the planes it is predicted from
+static int check_recon_not_ref(const char* fn, const uint8_t* const* refs, int nref, const uint8_t* out_recon) {
+    for (int i = 0; i < nref; ++i)
+        if (refs[i] == out_recon) {
+            set_error("%s: out_recon aliases refs[%d]", fn, i);
+            return SO_E_INVALID;
+        }
+    return SO_OK;
+}
 
-#define SO_NEED(p, fn)                                  \
-    do {                                                \
-        if (!(p)) {                                     \
-            set_error("%s: %s is NULL", fn, #p);        \
-            return SO_E_INVALID;                        \
-        }                                               \
-    } while (0)
+static int check_qp_clamp(const char* fn, int qp_lo, int qp_hi) {
+    if (qp_lo < 0 || qp_hi > 20 || qp_lo > qp_hi) {
+        set_error("%s: QP clamp [%d, %d] outside [0, 20]", fn, qp_lo, qp_hi);
+        return SO_E_INVALID;
+    }
+    return SO_OK;
+}
 
-// ---- per-frame sums of the encode kernels' per-block / per-row SSE ---------------------------
-constexpr int kSumMax = 64;
-struct SumArgs {
-    const int32_t* p[kSumMax];
+// a HIP runtime call's status as an entry point's return code, with the runtime's own text
+static int hip_status(const char* fn, hipError_t e) {
+    if (e == hipSuccess) return SO_OK;
+    set_error("%s: %s", fn, hipGetErrorString(e));
+    return (int)e;
+}
+
+// ---- the persistent runs' shared checks (so_encode_p_run*, the frame pipeline) ----------------
+// The scalar arguments.  The run kernels cover one configuration; `tail` is the caller's end of
+// that sentence; a two-pass run is built for W <= 8192 only.
+static int check_run(const char* fn, int H, int W, int bs, int sr, int qp_rd, int vbs, double lam, bool two_pass,
+                     const char* tail) {
+    SO_TRY(check_geom(fn, H, W, bs, vbs));
+    SO_TRY(check_vbs(fn, vbs, lam));
+    SO_TRY(check_sr(fn, sr));
+    SO_TRY(check_qp(fn, qp_rd));
+    if (bs != 16 || sr != 16 || W % 128 != 0 || (two_pass && W > 8192)) {
+        set_error("%s: covers bs 16 / sr 16 / W %% 128 == 0%s", fn, tail);
+        return SO_E_UNSUPPORTED;
+    }
+    return SO_OK;
+}
+
+// The arrays of per-frame pointers a run takes ([nframes] each; out_sse optional, out_qp_map
+// two-pass runs only).
+struct RunArrays {
+    const uint8_t* const* curs;
+    uint8_t* const* out_split;
+    int16_t* const* out_mv;
+    int16_t* const* out_qtc;
+    int32_t* const* out_tokens;
+    int32_t* const* out_mae_num;
+    uint8_t* const* out_recon;
+    int32_t* const* out_sse;
+    int32_t* const* out_qp_map;
 };
 
-// one workgroup of 1024 threads per array: int64 sum of len int32 values into out[blockIdx.x];
-// 16-byte loads, eight in flight per thread (a 4K frame's 32,400 per-block values are ~130 KB:
-// 256 threads left it latency-bound at 10 us for 30 frames)
-constexpr int kSumThreads = 1024;
-__global__ void __launch_bounds__(kSumThreads) sum_rows_kernel(const SumArgs a, int len, long long* __restrict__ out) {
-    __shared__ long long part[kSumThreads / 64];
-    const int32_t* p = a.p[blockIdx.x];
-    long long acc = 0;
-    const int n4 = (reinterpret_cast<uintptr_t>(p) & 15) ? 0 : len / 4;
-    const int4* p4 = reinterpret_cast<const int4*>(p);
-    int i = threadIdx.x;
-    // guarded loads, all eight issued before the adds (a separate remainder loop ran its loads
-    // one round trip at a time: 8 us for a 4K GOP's 30 frames)
-    for (; i < n4; i += 8 * kSumThreads) {
-        int4 v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = i + k * kSumThreads < n4 ? p4[i + k * kSumThreads] : make_int4(0, 0, 0, 0);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc += (long long)v[k].x + v[k].y + v[k].z + v[k].w;
-    }
-    for (int j = 4 * n4 + threadIdx.x; j < len; j += kSumThreads) acc += p[j];
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-#pragma unroll
-        for (int w = 0; w < kSumThreads / 64; ++w) t += part[w];
-        out[blockIdx.x] = t;
-    }
+static int need_run_outputs(const char* fn, const RunArrays& a) {
+    const auto& [curs, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, out_qp_map] = a;
+    SO_NEED(out_split, fn); SO_NEED(out_mv, fn); SO_NEED(out_qtc, fn); SO_NEED(out_tokens, fn);
+    SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn);
+    return SO_OK;
 }
 
-// ---- SSE (PSNR) -------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) sse_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
-                                                  int64_t n, unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long part[4];
-    unsigned long long acc = 0;
-    const int64_t n16 = n / 16;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) {
-        const uint4 va = reinterpret_cast<const uint4*>(a)[i];
-        const uint4 vb = reinterpret_cast<const uint4*>(b)[i];
-        const uint32_t wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
-        uint32_t s = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int d = (int)((wa[k] >> (8 * e)) & 255) - (int)((wb[k] >> (8 * e)) & 255);
-                s += (uint32_t)(d * d);
-            }
-        acc += s;
+// Frame by frame: no NULL entry, then the caller's own rule for frame i (`each`: aliasing,
+// landing planes, dependencies), then the kernels' record of the frame's outputs.
+template <class Each>
+static int run_frames(const char* fn, const RunArrays& a, int nframes, std::vector<PFrameOut>* outs, Each each) {
+    const auto& [curs, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, out_qp_map] = a;
+    outs->resize((size_t)nframes);
+    for (int i = 0; i < nframes; ++i) {
+        SO_NEED(curs[i], fn); SO_NEED(out_split[i], fn); SO_NEED(out_mv[i], fn); SO_NEED(out_qtc[i], fn);
+        SO_NEED(out_tokens[i], fn); SO_NEED(out_mae_num[i], fn); SO_NEED(out_recon[i], fn);
+        if (out_qp_map) SO_NEED(out_qp_map[i], fn);
+        SO_TRY(each(i));
+        (*outs)[(size_t)i] = PFrameOut{out_split[i], out_mv[i], out_qtc[i], out_tokens[i], out_mae_num[i], out_recon[i],
+                                       out_sse ? out_sse[i] : nullptr, out_qp_map ? out_qp_map[i] : nullptr};
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0)
-        for (int64_t i = n16 * 16; i < n; ++i) {
-            const int d = (int)a[i] - (int)b[i];
-            acc += (unsigned long long)(d * d);
-        }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, part[0] + part[1] + part[2] + part[3]);
+    return SO_OK;
 }
 
-// Per-block QP map (build extension, DESIGN.md "ROI and two-pass rate control"): one
-// workgroup per block row.  Two-pass: with pass-1 token counts t (stripe-local records) the
-// row mean is m / n (m = sum, n = blocks per row) and
-//   delta = [t n >= 2m] + [t n >= 4m] - [2 t n < m] - [4 t n < m]      (in [-2, 2], exact)
-// i.e. blocks at >= 2x / 4x the row's mean bits are quantised 1 / 2 QP coarser and blocks at
-// < 1/2 / < 1/4 of it 1 / 2 QP finer.  qp = clamp(base + delta + roi, qp_lo, qp_hi) with
-// base = qp_row[by] (rate-control schedule) or qp_rd.  tokens == NULL: ROI only (delta 0).
-__global__ void __launch_bounds__(256)
-qp_map_kernel(const int32_t* __restrict__ tokens, int nbx, int by0, int qp_rd, const int32_t* __restrict__ qp_row,
-              const int32_t* __restrict__ roi, int qp_lo, int qp_hi, int32_t* __restrict__ out) {
-    __shared__ long long part[4];
-    const int by = by0 + blockIdx.x;
-    const int32_t* t = tokens ? tokens + (size_t)blockIdx.x * nbx : nullptr;
-    long long m = 0;
-    if (t) {
-        for (int bx = threadIdx.x; bx < nbx; bx += blockDim.x) m += t[bx];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) m += __shfl_xor(m, s, 64);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-        __syncthreads();
-        m = part[0] + part[1] + part[2] + part[3];
-    }
-    const int base = qp_row ? qp_row[by] : qp_rd;
-    for (int bx = threadIdx.x; bx < nbx; bx += blockDim.x) {
-        int d = 0;
-        if (t) {
-            const long long tn = (long long)t[bx] * nbx;
-            d = (tn >= 2 * m) + (tn >= 4 * m) - (2 * tn < m) - (4 * tn < m);
+// a chain from ref0: frame i's reconstruction is neither ref0 nor an earlier frame's
+static int check_chain_alias(const char* fn, const uint8_t* ref0, uint8_t* const* out_recon, int i) {
+    for (int j = -1; j < i; ++j)
+        if (out_recon[i] == (j < 0 ? ref0 : out_recon[j])) {
+            set_error("%s: out_recon[%d] aliases ref0 or another frame's reconstruction", fn, i);
+            return SO_E_INVALID;
         }
-        int q = base + d + (roi ? roi[(size_t)by * nbx + bx] : 0);
-        q = q < qp_lo ? qp_lo : (q > qp_hi ? qp_hi : q);
-        out[(size_t)by * nbx + bx] = q;
+    return SO_OK;
+}
+
+// ---- aliasing of pictures given as address spans (colour conversion, scaling) -----------------
+struct Span {
+    uintptr_t lo, hi;   // [lo, hi)
+    bool dst;
+    const char* what;
+    int frame;
+};
+
+// A destination may share no byte with a source or another destination; sources may repeat.
+// dst_vs_dst false leaves destination against destination to the caller (whose destinations may
+// interleave inside one span).
+static int check_spans(const char* fn, std::vector<Span>& spans, bool dst_vs_dst) {
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.lo < b.lo; });
+    // the furthest end so far of a source, of a destination, and which span it belongs to
+    const Span *far_src = nullptr, *far_dst = nullptr;
+    for (const Span& s : spans) {
+        const Span* hit = nullptr;
+        if (far_dst && s.lo < far_dst->hi && (!s.dst || dst_vs_dst)) hit = far_dst;
+        if (!hit && s.dst && far_src && s.lo < far_src->hi) hit = far_src;
+        if (hit) {
+            set_error("%s: %s[%d] aliases %s[%d] (a destination overlaps a source or another destination)", fn,
+                      s.what, s.frame, hit->what, hit->frame);
+            return SO_E_INVALID;
+        }
+        const Span*& far = s.dst ? far_dst : far_src;
+        if (!far || s.hi > far->hi) far = &s;
     }
+    return SO_OK;
 }
 
 }  // namespace so
@@ -356,11 +311,7 @@ int so_inter_tq_recon(const uint8_t* cur, const uint8_t* const* refs, int nref, 
     if (vbs) SO_NEED(sub, fn);
     RefSet rs;
     SO_TRY(make_refs(fn, refs, nref, &rs));
-    for (int i = 0; i < nref; ++i)
-        if (refs[i] == out_recon) {
-            set_error("%s: out_recon aliases refs[%d]", fn, i);
-            return SO_E_INVALID;
-        }
+    SO_TRY(check_recon_not_ref(fn, refs, nref, out_recon));
     return inter_tq_launch(cur, rs, nullptr, 0, H, W, bs, 0, H / bs, best, vbs ? sub : nullptr, qp_rd, qp_row, nullptr, vbs, lam,
                            out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse,
                            (hipStream_t)stream);
@@ -370,36 +321,6 @@ size_t so_p_frame_scratch_elems(int H, int W, int bs, int vbs) {
     if (bs <= 0) return 0;
     const size_t nb = (size_t)(W / bs) * (size_t)(H / bs);
     return nb * 4 + (vbs ? nb * 16 : 0) + kFastSegWords;
-}
-
-int so_encode_p_rows(const uint8_t* cur, const uint8_t* const* refs, int nref, int H, int W, int bs, int sr,
-                     int by0, int by1, int qp_rd, const int32_t* qp_row, int vbs, double lam, uint8_t* out_split,
-                     int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num,
-                     uint8_t* out_recon, int32_t* out_sse, int32_t* scratch, void* stream) {
-    const char* fn = "so_encode_p_rows";
-    SO_TRY(check_geom(fn, H, W, bs, vbs));
-    SO_TRY(check_sr(fn, sr));
-    SO_TRY(check_qp(fn, qp_rd));
-    SO_TRY(check_rows(fn, H, bs, by0, by1));
-    SO_NEED(cur, fn); SO_NEED(scratch, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn);
-    SO_NEED(out_qtc, fn); SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn);
-    RefSet rs;
-    SO_TRY(make_refs(fn, refs, nref, &rs));
-    for (int i = 0; i < nref; ++i)
-        if (refs[i] == out_recon) {
-            set_error("%s: out_recon aliases refs[%d]", fn, i);
-            return SO_E_INVALID;
-        }
-    const size_t nbs = (size_t)(W / bs) * (size_t)(by1 - by0);
-    int32_t* best = scratch;
-    int32_t* sub = vbs ? scratch + nbs * 4 : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (use_fused(bs, sr, vbs, nref))
-        return p_tile_launch(cur, rs, H, W, by0, by1, qp_rd, qp_row, nullptr, best, out_split, out_mv, out_qtc,
-                             out_tokens, out_mae_num, out_recon, out_sse, st);
-    SO_TRY(me_launch(cur, rs, nref, H, W, bs, sr, by0, by1, best, sub, st));
-    return inter_tq_launch(cur, rs, nullptr, 0, H, W, bs, by0, by1, best, sub, qp_rd, qp_row, nullptr, vbs, lam, out_split,
-                           out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, st);
 }
 
 int so_encode_p_frame(const uint8_t* cur, const uint8_t* const* refs, int nref, int H, int W, int bs, int sr,
@@ -465,29 +386,14 @@ int so_encode_p_run(const uint8_t* const* curs, int nframes, const uint8_t* ref0
                     int32_t* const* out_mae_num, uint8_t* const* out_recon, int32_t* const* out_sse,
                     uint32_t* workspace, void* stream) {
     const char* fn = "so_encode_p_run";
-    SO_TRY(check_geom(fn, H, W, bs, vbs));
-    SO_TRY(check_vbs(fn, vbs, lam));
-    SO_TRY(check_sr(fn, sr));
-    SO_TRY(check_qp(fn, qp_rd));
-    if (bs != 16 || sr != 16 || W % 128 != 0) {
-        set_error("%s: covers bs 16 / sr 16 / W %% 128 == 0 (call so_encode_p_frame per frame)", fn);
-        return SO_E_UNSUPPORTED;
-    }
+    SO_TRY(check_run(fn, H, W, bs, sr, qp_rd, vbs, lam, false, " (call so_encode_p_frame per frame)"));
     if (nframes <= 0) return SO_OK;
-    SO_NEED(curs, fn); SO_NEED(ref0, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn); SO_NEED(out_qtc, fn);
-    SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn); SO_NEED(workspace, fn);
-    std::vector<PFrameOut> outs((size_t)nframes);
-    for (int i = 0; i < nframes; ++i) {
-        SO_NEED(curs[i], fn); SO_NEED(out_split[i], fn); SO_NEED(out_mv[i], fn); SO_NEED(out_qtc[i], fn);
-        SO_NEED(out_tokens[i], fn); SO_NEED(out_mae_num[i], fn); SO_NEED(out_recon[i], fn);
-        for (int j = -1; j < i; ++j)
-            if (out_recon[i] == (j < 0 ? ref0 : out_recon[j])) {
-                set_error("%s: out_recon[%d] aliases ref0 or another frame's reconstruction", fn, i);
-                return SO_E_INVALID;
-            }
-        outs[i] = PFrameOut{out_split[i], out_mv[i], out_qtc[i], out_tokens[i], out_mae_num[i], out_recon[i],
-                            out_sse ? out_sse[i] : nullptr};
-    }
+    const RunArrays a{curs, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, nullptr};
+    SO_NEED(curs, fn); SO_NEED(ref0, fn);
+    SO_TRY(need_run_outputs(fn, a));
+    SO_NEED(workspace, fn);
+    std::vector<PFrameOut> outs;
+    SO_TRY(run_frames(fn, a, nframes, &outs, [&](int i) { return check_chain_alias(fn, ref0, out_recon, i); }));
     return p_run_launch(curs, nframes, ref0, H, W, qp_rd, qp_row, vbs, lam, outs.data(), workspace,
                         (hipStream_t)stream);
 }
@@ -498,24 +404,16 @@ int so_encode_p_runs(const uint8_t* const* curs, int nframes, const uint8_t* con
                      int32_t* const* out_tokens, int32_t* const* out_mae_num, uint8_t* const* out_recon,
                      int32_t* const* out_sse, uint32_t* workspace, void* stream) {
     const char* fn = "so_encode_p_runs";
-    SO_TRY(check_geom(fn, H, W, bs, vbs));
-    SO_TRY(check_vbs(fn, vbs, lam));
-    SO_TRY(check_sr(fn, sr));
-    SO_TRY(check_qp(fn, qp_rd));
-    if (bs != 16 || sr != 16 || W % 128 != 0) {
-        set_error("%s: covers bs 16 / sr 16 / W %% 128 == 0 (call so_encode_p_frame per frame)", fn);
-        return SO_E_UNSUPPORTED;
-    }
+    SO_TRY(check_run(fn, H, W, bs, sr, qp_rd, vbs, lam, false, " (call so_encode_p_frame per frame)"));
     if (nframes <= 0) return SO_OK;
-    SO_NEED(curs, fn); SO_NEED(refs, fn); SO_NEED(ref_frame, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn);
-    SO_NEED(out_qtc, fn); SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn);
+    const RunArrays a{curs, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, nullptr};
+    SO_NEED(curs, fn); SO_NEED(refs, fn); SO_NEED(ref_frame, fn);
+    SO_TRY(need_run_outputs(fn, a));
     SO_NEED(workspace, fn);
-    std::vector<PFrameOut> outs((size_t)nframes);
+    std::vector<PFrameOut> outs;
     std::vector<int> deps((size_t)nframes);
     int conc = 0;   // runs starting from a plane outside the list: interleaved chains
-    for (int i = 0; i < nframes; ++i) {
-        SO_NEED(curs[i], fn); SO_NEED(out_split[i], fn); SO_NEED(out_mv[i], fn); SO_NEED(out_qtc[i], fn);
-        SO_NEED(out_tokens[i], fn); SO_NEED(out_mae_num[i], fn); SO_NEED(out_recon[i], fn);
+    SO_TRY(run_frames(fn, a, nframes, &outs, [&](int i) {
         const int d = ref_frame[i];
         if (d >= i || d < -1) {
             set_error("%s: ref_frame[%d] = %d (must be -1 or an earlier frame of the list)", fn, i, d);
@@ -531,9 +429,8 @@ int so_encode_p_runs(const uint8_t* const* curs, int nframes, const uint8_t* con
                 set_error("%s: out_recon[%d] aliases a reference plane or another frame's reconstruction", fn, i);
                 return SO_E_INVALID;
             }
-        outs[(size_t)i] = PFrameOut{out_split[i], out_mv[i], out_qtc[i], out_tokens[i], out_mae_num[i], out_recon[i],
-                                    out_sse ? out_sse[i] : nullptr};
-    }
+        return SO_OK;
+    }));
     return p_runs_launch(curs, nframes, refs, deps.data(), conc, H, W, qp_rd, qp_row, vbs, lam, outs.data(), workspace,
                          (hipStream_t)stream);
 }
@@ -544,33 +441,15 @@ int so_encode_p_run_2pass(const uint8_t* const* curs, int nframes, const uint8_t
                           int32_t* const* out_tokens, int32_t* const* out_mae_num, uint8_t* const* out_recon,
                           int32_t* const* out_sse, int32_t* const* out_qp_map, uint32_t* workspace, void* stream) {
     const char* fn = "so_encode_p_run_2pass";
-    SO_TRY(check_geom(fn, H, W, bs, 0));
-    SO_TRY(check_sr(fn, sr));
-    SO_TRY(check_qp(fn, qp_rd));
-    if (bs != 16 || sr != 16 || W % 128 != 0 || W > 8192) {
-        set_error("%s: covers bs 16 / sr 16 / W %% 128 == 0, W <= 8192 (encode per frame otherwise)", fn);
-        return SO_E_UNSUPPORTED;
-    }
-    if (qp_lo < 0 || qp_hi > 20 || qp_lo > qp_hi) {
-        set_error("%s: QP clamp [%d, %d] outside [0, 20]", fn, qp_lo, qp_hi);
-        return SO_E_INVALID;
-    }
+    SO_TRY(check_run(fn, H, W, bs, sr, qp_rd, 0, 0.0, true, ", W <= 8192 (encode per frame otherwise)"));
+    SO_TRY(check_qp_clamp(fn, qp_lo, qp_hi));
     if (nframes <= 0) return SO_OK;
-    SO_NEED(curs, fn); SO_NEED(ref0, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn); SO_NEED(out_qtc, fn);
-    SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn); SO_NEED(out_qp_map, fn);
-    SO_NEED(workspace, fn);
-    std::vector<PFrameOut> outs((size_t)nframes);
-    for (int i = 0; i < nframes; ++i) {
-        SO_NEED(curs[i], fn); SO_NEED(out_split[i], fn); SO_NEED(out_mv[i], fn); SO_NEED(out_qtc[i], fn);
-        SO_NEED(out_tokens[i], fn); SO_NEED(out_mae_num[i], fn); SO_NEED(out_recon[i], fn); SO_NEED(out_qp_map[i], fn);
-        for (int j = -1; j < i; ++j)
-            if (out_recon[i] == (j < 0 ? ref0 : out_recon[j])) {
-                set_error("%s: out_recon[%d] aliases ref0 or another frame's reconstruction", fn, i);
-                return SO_E_INVALID;
-            }
-        outs[(size_t)i] = PFrameOut{out_split[i], out_mv[i], out_qtc[i], out_tokens[i], out_mae_num[i], out_recon[i],
-                                    out_sse ? out_sse[i] : nullptr, out_qp_map[i]};
-    }
+    const RunArrays a{curs, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, out_qp_map};
+    SO_NEED(curs, fn); SO_NEED(ref0, fn);
+    SO_TRY(need_run_outputs(fn, a));
+    SO_NEED(out_qp_map, fn); SO_NEED(workspace, fn);
+    std::vector<PFrameOut> outs;
+    SO_TRY(run_frames(fn, a, nframes, &outs, [&](int i) { return check_chain_alias(fn, ref0, out_recon, i); }));
     hipStream_t st = (hipStream_t)stream;
     // default: both passes of every frame in one persistent launch (each task the pass 2 of one
     // tile and the pass 1 of another), for frames of three tile rows or
@@ -611,13 +490,7 @@ int so_encode_p_run_stripe(const uint8_t* const* curs, int nframes, const uint8_
                            const uint32_t* my_up_flags, const uint32_t* my_dn_flags, uint32_t* peer_up_flags,
                            uint32_t* peer_dn_flags, uint32_t epoch, int max_wg, void* stream) {
     const char* fn = "so_encode_p_run_stripe";
-    SO_TRY(check_geom(fn, H, W, bs, 0));
-    SO_TRY(check_sr(fn, sr));
-    SO_TRY(check_qp(fn, qp_rd));
-    if (bs != 16 || sr != 16 || W % 128 != 0) {
-        set_error("%s: covers bs 16 / sr 16 / W %% 128 == 0", fn);
-        return SO_E_UNSUPPORTED;
-    }
+    SO_TRY(check_run(fn, H, W, bs, sr, qp_rd, 0, 0.0, false, ""));
     if (by0 < 0 || by1 > H / 16 || by1 <= by0 || gbase < 1) {
         set_error("%s: bad stripe [%d, %d) of %d block rows or gbase %d", fn, by0, by1, H / 16, gbase);
         return SO_E_INVALID;
@@ -629,15 +502,12 @@ int so_encode_p_run_stripe(const uint8_t* const* curs, int nframes, const uint8_
         return SO_E_INVALID;
     }
     if (nframes <= 0) return SO_OK;
-    SO_NEED(curs, fn); SO_NEED(ref0, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn); SO_NEED(out_qtc, fn);
-    SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn); SO_NEED(workspace, fn);
-    std::vector<PFrameOut> outs((size_t)nframes);
-    for (int i = 0; i < nframes; ++i) {
-        SO_NEED(curs[i], fn); SO_NEED(out_split[i], fn); SO_NEED(out_mv[i], fn); SO_NEED(out_qtc[i], fn);
-        SO_NEED(out_tokens[i], fn); SO_NEED(out_mae_num[i], fn); SO_NEED(out_recon[i], fn);
-        outs[i] = PFrameOut{out_split[i], out_mv[i], out_qtc[i], out_tokens[i], out_mae_num[i], out_recon[i],
-                            out_sse ? out_sse[i] : nullptr};
-    }
+    const RunArrays a{curs, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, nullptr};
+    SO_NEED(curs, fn); SO_NEED(ref0, fn);
+    SO_TRY(need_run_outputs(fn, a));
+    SO_NEED(workspace, fn);
+    std::vector<PFrameOut> outs;
+    SO_TRY(run_frames(fn, a, nframes, &outs, [](int) { return SO_OK; }));
     PRunStripe sp{by0, by1, peer_up0, peer_dn0, stride, my_up_flags, my_dn_flags, peer_up_flags, peer_dn_flags,
                   epoch, gbase, nullptr};
     return p_run_stripe_launch(curs, nframes, ref0, H, W, qp_rd, qp_row, outs.data(), workspace, sp, max_wg,
@@ -674,22 +544,9 @@ static int fpipe_run(const char* fn, bool two_pass, const uint8_t* const* curs, 
                      const uint32_t* land_flags, int slot0, uint8_t* peer_land0, uint32_t* peer_flags,
                      uint8_t* peer2_land0, uint32_t* peer2_flags, const int32_t* push_to, int nslots, long long stride,
                      uint32_t epoch, int max_wg, int p2lag, void* stream) {
-    SO_TRY(check_geom(fn, H, W, bs, vbs));
-    SO_TRY(check_vbs(fn, vbs, lam));
-    SO_TRY(check_sr(fn, sr));
-    SO_TRY(check_qp(fn, qp_rd));
-    if (two_pass && vbs) {
-        set_error("%s: two-pass RC with VBSEnable is not built for the frame pipeline", fn);
-        return SO_E_UNSUPPORTED;
-    }
-    if (bs != 16 || sr != 16 || W % 128 != 0 || (two_pass && W > 8192)) {
-        set_error("%s: covers bs 16 / sr 16 / W %% 128 == 0%s", fn, two_pass ? ", W <= 8192" : "");
-        return SO_E_UNSUPPORTED;
-    }
-    if (two_pass && (qp_lo < 0 || qp_hi > 20 || qp_lo > qp_hi)) {
-        set_error("%s: QP clamp [%d, %d] outside [0, 20]", fn, qp_lo, qp_hi);
-        return SO_E_INVALID;
-    }
+    // two-pass RC with VBSEnable is not built for the frame pipeline: its entry point takes no vbs
+    SO_TRY(check_run(fn, H, W, bs, sr, qp_rd, vbs, lam, two_pass, two_pass ? ", W <= 8192" : ""));
+    if (two_pass) SO_TRY(check_qp_clamp(fn, qp_lo, qp_hi));
     // every rank owns `nslots` landing slots: this run reads slots [slot0, slot0 + nframes) and
     // writes (system scope, over xGMI) only slots below nslots of its peers
     if (p2lag < 0) {
@@ -701,18 +558,18 @@ static int fpipe_run(const char* fn, bool two_pass, const uint8_t* const* curs, 
         return SO_E_INVALID;
     }
     if (nframes <= 0) return SO_OK;
-    SO_NEED(curs, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn); SO_NEED(out_qtc, fn); SO_NEED(out_tokens, fn);
-    SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn); SO_NEED(workspace, fn); SO_NEED(land0, fn);
+    const RunArrays a{curs, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse,
+                      two_pass ? out_qp_map : nullptr};
+    SO_NEED(curs, fn);
+    SO_TRY(need_run_outputs(fn, a));
+    SO_NEED(workspace, fn); SO_NEED(land0, fn);
     SO_NEED(land_flags, fn); SO_NEED(peer_land0, fn); SO_NEED(peer_flags, fn); SO_NEED(peer2_land0, fn);
     SO_NEED(peer2_flags, fn); SO_NEED(push_to, fn);
     if (two_pass) SO_NEED(out_qp_map, fn);
-    std::vector<PFrameOut> outs((size_t)nframes);
+    std::vector<PFrameOut> outs;
     std::vector<int> push((size_t)nframes);
     const uint8_t* land_end = land0 + (long long)(slot0 + nframes) * stride;
-    for (int i = 0; i < nframes; ++i) {
-        SO_NEED(curs[i], fn); SO_NEED(out_split[i], fn); SO_NEED(out_mv[i], fn); SO_NEED(out_qtc[i], fn);
-        SO_NEED(out_tokens[i], fn); SO_NEED(out_mae_num[i], fn); SO_NEED(out_recon[i], fn);
-        if (two_pass) SO_NEED(out_qp_map[i], fn);
+    SO_TRY(run_frames(fn, a, nframes, &outs, [&](int i) {
         if (out_recon[i] >= land0 && out_recon[i] < land_end) {
             set_error("%s: out_recon[%d] lies in the landing planes", fn, i);
             return SO_E_INVALID;
@@ -722,9 +579,8 @@ static int fpipe_run(const char* fn, bool two_pass, const uint8_t* const* curs, 
             return SO_E_INVALID;
         }
         push[(size_t)i] = push_to[i];
-        outs[i] = PFrameOut{out_split[i], out_mv[i], out_qtc[i], out_tokens[i], out_mae_num[i], out_recon[i],
-                            out_sse ? out_sse[i] : nullptr, two_pass ? out_qp_map[i] : nullptr};
-    }
+        return SO_OK;
+    }));
     PRunStripe sp{0, H / 16, peer2_land0, peer_land0, stride, nullptr, land_flags, peer2_flags, peer_flags,
                   epoch, slot0, land0};
     if (two_pass) {
@@ -795,12 +651,7 @@ int so_alloc_uncached(size_t bytes, void** out) {
 }
 
 int so_free_device(void* p) {
-    const hipError_t e = hipFree(p);
-    if (e != hipSuccess) {
-        set_error("so_free_device: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    return SO_OK;
+    return hip_status("so_free_device", hipFree(p));
 }
 
 int so_ipc_export(void* p, uint8_t* out_handle) {
@@ -810,11 +661,7 @@ int so_ipc_export(void* p, uint8_t* out_handle) {
         return SO_E_INVALID;
     }
     hipIpcMemHandle_t h;
-    const hipError_t e = hipIpcGetMemHandle(&h, p);
-    if (e != hipSuccess) {
-        set_error("so_ipc_export: %s", hipGetErrorString(e));
-        return (int)e;
-    }
+    SO_TRY(hip_status("so_ipc_export", hipIpcGetMemHandle(&h, p)));
     memset(out_handle, 0, SO_IPC_HANDLE_BYTES);
     memcpy(out_handle, &h, sizeof(h));
     return SO_OK;
@@ -827,12 +674,7 @@ int so_ipc_open(const uint8_t* handle, void** out) {
     }
     hipIpcMemHandle_t h;
     memcpy(&h, handle, sizeof(h));
-    const hipError_t e = hipIpcOpenMemHandle(out, h, hipIpcMemLazyEnablePeerAccess);
-    if (e != hipSuccess) {
-        set_error("so_ipc_open: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    return SO_OK;
+    return hip_status("so_ipc_open", hipIpcOpenMemHandle(out, h, hipIpcMemLazyEnablePeerAccess));
 }
 
 int so_copy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
@@ -840,30 +682,15 @@ int so_copy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
         set_error("so_copy_d2d: bad arguments");
         return SO_E_INVALID;
     }
-    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error("so_copy_d2d: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    return SO_OK;
+    return hip_status("so_copy_d2d", hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
 }
 
 int so_memset_d8(void* dst, int value, size_t bytes, void* stream) {
-    const hipError_t e = hipMemsetAsync(dst, value, bytes, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        set_error("so_memset_d8: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    return SO_OK;
+    return hip_status("so_memset_d8", hipMemsetAsync(dst, value, bytes, (hipStream_t)stream));
 }
 
 int so_ipc_close(void* p) {
-    const hipError_t e = hipIpcCloseMemHandle(p);
-    if (e != hipSuccess) {
-        set_error("so_ipc_close: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    return SO_OK;
+    return hip_status("so_ipc_close", hipIpcCloseMemHandle(p));
 }
 
 size_t so_i_frame_scratch_elems(int H, int W, int bs) {
@@ -872,11 +699,11 @@ size_t so_i_frame_scratch_elems(int H, int W, int bs) {
     return nb * (size_t)bs * bs + nb * 8;
 }
 
-int so_encode_i_rows(const uint8_t* cur, int H, int W, int bs, int sr, int by0, int by1, int qp_rd,
-                     const int32_t* qp_row, int vbs, double lam, uint8_t* out_split, int16_t* out_mv,
-                     int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num, uint8_t* out_recon,
-                     int32_t* out_sse, int32_t* scratch, void* stream) {
-    const char* fn = "so_encode_i_rows";
+// ---- the base entry points and their _ex forms (per-block QP map, ME variants, FME) ---------
+static int i_rows(const char* fn, const uint8_t* cur, int H, int W, int bs, int sr, int by0, int by1, int qp_rd,
+                  const int32_t* qp_row, const int32_t* qp_map, int vbs, double lam, uint8_t* out_split,
+                  int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num, uint8_t* out_recon,
+                  int32_t* out_sse, int32_t* scratch, void* stream) {
     SO_TRY(check_geom(fn, H, W, bs, vbs));
     SO_TRY(check_intra_width(fn, W));
     SO_TRY(check_sr(fn, sr));
@@ -884,9 +711,25 @@ int so_encode_i_rows(const uint8_t* cur, int H, int W, int bs, int sr, int by0, 
     SO_TRY(check_rows(fn, H, bs, by0, by1));
     SO_NEED(cur, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn); SO_NEED(out_qtc, fn);
     SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn); SO_NEED(scratch, fn);
-    return intra_encode_launch(cur, H, W, bs, sr, by0, by1, qp_rd, qp_row, nullptr, vbs, lam, out_split, out_mv, out_qtc,
-                               out_tokens, out_mae_num, out_recon, out_sse, reinterpret_cast<uint8_t*>(scratch),
+    return intra_encode_launch(cur, H, W, bs, sr, by0, by1, qp_rd, qp_row, qp_map, vbs, lam, out_split, out_mv,
+                               out_qtc, out_tokens, out_mae_num, out_recon, out_sse, reinterpret_cast<uint8_t*>(scratch),
                                (hipStream_t)stream);
+}
+
+int so_encode_i_rows(const uint8_t* cur, int H, int W, int bs, int sr, int by0, int by1, int qp_rd,
+                     const int32_t* qp_row, int vbs, double lam, uint8_t* out_split, int16_t* out_mv,
+                     int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num, uint8_t* out_recon,
+                     int32_t* out_sse, int32_t* scratch, void* stream) {
+    return i_rows("so_encode_i_rows", cur, H, W, bs, sr, by0, by1, qp_rd, qp_row, nullptr, vbs, lam, out_split, out_mv,
+                  out_qtc, out_tokens, out_mae_num, out_recon, out_sse, scratch, stream);
+}
+
+int so_encode_i_rows_ex(const uint8_t* cur, int H, int W, int bs, int sr, int by0, int by1, int qp_rd,
+                        const int32_t* qp_row, const int32_t* qp_map, int vbs, double lam, uint8_t* out_split,
+                        int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num,
+                        uint8_t* out_recon, int32_t* out_sse, int32_t* scratch, void* stream) {
+    return i_rows("so_encode_i_rows_ex", cur, H, W, bs, sr, by0, by1, qp_rd, qp_row, qp_map, vbs, lam, out_split,
+                  out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse, scratch, stream);
 }
 
 int so_encode_i_frame(const uint8_t* cur, int H, int W, int bs, int sr, int qp_rd, const int32_t* qp_row,
@@ -901,28 +744,58 @@ int so_encode_i_frame(const uint8_t* cur, int H, int W, int bs, int sr, int qp_r
                             out_tokens, out_mae_num, out_recon, out_sse, scratch, stream);
 }
 
-int so_inter_recon(const uint8_t* const* refs, int nref, int H, int W, int bs, int qp, const int32_t* qp_row,
-                   const uint8_t* split, const int16_t* mv, const int16_t* qtc, uint8_t* out_recon, void* stream) {
-    const char* fn = "so_inter_recon";
+static int inter_recon(const char* fn, const uint8_t* const* refs, int nref, int H, int W, int bs, int qp,
+                       const int32_t* qp_row, const int32_t* qp_map, int fme, int fme_wrap, uint8_t* fme_planes,
+                       const uint8_t* split, const int16_t* mv, const int16_t* qtc, uint8_t* out_recon, void* stream) {
     SO_TRY(check_geom(fn, H, W, bs, 0));
     SO_TRY(check_qp(fn, qp));
     SO_NEED(split, fn); SO_NEED(mv, fn); SO_NEED(qtc, fn); SO_NEED(out_recon, fn);
+    if (fme) SO_NEED(fme_planes, fn);
     RefSet rs;
     SO_TRY(make_refs(fn, refs, nref, &rs));
-    return inter_recon_launch(rs, nullptr, 0, H, W, bs, qp, qp_row, nullptr, split, mv, qtc, out_recon,
-                              (hipStream_t)stream);
+    const size_t ps = so_fme_plane_stride(H, W);   // read by the FME kernels only
+    hipStream_t st = (hipStream_t)stream;
+    if (fme)
+        for (int r = 0; r < nref; ++r)
+            SO_TRY(fme_planes_launch(refs[r], H, W, fme_wrap, fme_planes + (size_t)r * 4 * ps, ps, st));
+    return inter_recon_launch(rs, fme ? fme_planes : nullptr, ps, H, W, bs, qp, qp_row, qp_map, split, mv, qtc,
+                              out_recon, st);
 }
 
-int so_intra_recon(int H, int W, int bs, int qp, const int32_t* qp_row, const uint8_t* split, const int16_t* mv,
-                   const int16_t* qtc, uint8_t* out_recon, int32_t* scratch, void* stream) {
-    const char* fn = "so_intra_recon";
+int so_inter_recon(const uint8_t* const* refs, int nref, int H, int W, int bs, int qp, const int32_t* qp_row,
+                   const uint8_t* split, const int16_t* mv, const int16_t* qtc, uint8_t* out_recon, void* stream) {
+    return inter_recon("so_inter_recon", refs, nref, H, W, bs, qp, qp_row, nullptr, 0, 0, nullptr, split, mv, qtc,
+                       out_recon, stream);
+}
+
+int so_inter_recon_ex(const uint8_t* const* refs, int nref, int H, int W, int bs, int qp, const int32_t* qp_row,
+                      const int32_t* qp_map, int fme, int fme_wrap, uint8_t* fme_planes, const uint8_t* split, const int16_t* mv,
+                      const int16_t* qtc, uint8_t* out_recon, void* stream) {
+    return inter_recon("so_inter_recon_ex", refs, nref, H, W, bs, qp, qp_row, qp_map, fme, fme_wrap, fme_planes, split,
+                       mv, qtc, out_recon, stream);
+}
+
+static int intra_recon(const char* fn, int H, int W, int bs, int qp, const int32_t* qp_row, const int32_t* qp_map,
+                       const uint8_t* split, const int16_t* mv, const int16_t* qtc, uint8_t* out_recon,
+                       int32_t* scratch, void* stream) {
     SO_TRY(check_geom(fn, H, W, bs, 0));
     SO_TRY(check_intra_width(fn, W));
     SO_TRY(check_qp(fn, qp));
     SO_NEED(split, fn); SO_NEED(mv, fn); SO_NEED(qtc, fn); SO_NEED(out_recon, fn); SO_NEED(scratch, fn);
     // the recon kernel only needs sr to size its ring: the largest reachable offset is 64
-    return intra_recon_launch(H, W, bs, 64, qp, qp_row, nullptr, split, mv, qtc, out_recon,
+    return intra_recon_launch(H, W, bs, 64, qp, qp_row, qp_map, split, mv, qtc, out_recon,
                               reinterpret_cast<uint8_t*>(scratch), (hipStream_t)stream);
+}
+
+int so_intra_recon(int H, int W, int bs, int qp, const int32_t* qp_row, const uint8_t* split, const int16_t* mv,
+                   const int16_t* qtc, uint8_t* out_recon, int32_t* scratch, void* stream) {
+    return intra_recon("so_intra_recon", H, W, bs, qp, qp_row, nullptr, split, mv, qtc, out_recon, scratch, stream);
+}
+
+int so_intra_recon_ex(int H, int W, int bs, int qp, const int32_t* qp_row, const int32_t* qp_map,
+                      const uint8_t* split, const int16_t* mv, const int16_t* qtc, uint8_t* out_recon,
+                      int32_t* scratch, void* stream) {
+    return intra_recon("so_intra_recon_ex", H, W, bs, qp, qp_row, qp_map, split, mv, qtc, out_recon, scratch, stream);
 }
 
 size_t so_fme_plane_stride(int H, int W) {
@@ -1003,15 +876,12 @@ int so_me_search_ex(const uint8_t* cur, const uint8_t* const* refs, int nref, in
                  out_sub, (hipStream_t)stream);
 }
 
-int so_encode_p_rows_ex(const uint8_t* cur, const uint8_t* const* refs, int nref, int H, int W, int bs, int sr,
-                        int by0, int by1, int qp_rd, const int32_t* qp_row, const int32_t* qp_map, int vbs, double lam,
-                        int me_mode, int fme, int fme_wrap, uint8_t* fme_planes, int flags, uint8_t* out_split, int16_t* out_mv, int16_t* out_qtc,
-                        int32_t* out_tokens, int32_t* out_mae_num, uint8_t* out_recon, int32_t* out_sse,
-                        int32_t* scratch, void* stream) {
-    const char* fn = "so_encode_p_rows_ex";
-    if (me_mode == SO_ME_FULL && !fme && !qp_map && !(flags & (SO_REUSE_ME | SO_TOKENS_ONLY)))
-        return so_encode_p_rows(cur, refs, nref, H, W, bs, sr, by0, by1, qp_rd, qp_row, vbs, lam, out_split, out_mv,
-                                out_qtc, out_tokens, out_mae_num, out_recon, out_sse, scratch, stream);
+// `fn` names the entry point refusals are reported under
+static int p_rows(const char* fn, const uint8_t* cur, const uint8_t* const* refs, int nref, int H, int W, int bs, int sr,
+                  int by0, int by1, int qp_rd, const int32_t* qp_row, const int32_t* qp_map, int vbs, double lam,
+                  int me_mode, int fme, int fme_wrap, uint8_t* fme_planes, int flags, uint8_t* out_split,
+                  int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num, uint8_t* out_recon,
+                  int32_t* out_sse, int32_t* scratch, void* stream) {
     SO_TRY(check_geom(fn, H, W, bs, vbs));
     SO_TRY(check_sr(fn, sr));
     SO_TRY(check_qp(fn, qp_rd));
@@ -1020,11 +890,7 @@ int so_encode_p_rows_ex(const uint8_t* cur, const uint8_t* const* refs, int nref
     SO_NEED(out_qtc, fn); SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn);
     RefSet rs;
     SO_TRY(make_refs(fn, refs, nref, &rs));
-    for (int i = 0; i < nref; ++i)
-        if (refs[i] == out_recon) {
-            set_error("%s: out_recon aliases refs[%d]", fn, i);
-            return SO_E_INVALID;
-        }
+    SO_TRY(check_recon_not_ref(fn, refs, nref, out_recon));
     const size_t nbs = (size_t)(W / bs) * (size_t)(by1 - by0);
     int32_t* best = scratch;
     int32_t* sub = vbs ? scratch + nbs * 4 : nullptr;
@@ -1044,52 +910,25 @@ int so_encode_p_rows_ex(const uint8_t* cur, const uint8_t* const* refs, int nref
                            out_sse, st);
 }
 
-int so_inter_recon_ex(const uint8_t* const* refs, int nref, int H, int W, int bs, int qp, const int32_t* qp_row,
-                      const int32_t* qp_map, int fme, int fme_wrap, uint8_t* fme_planes, const uint8_t* split, const int16_t* mv,
-                      const int16_t* qtc, uint8_t* out_recon, void* stream) {
-    const char* fn = "so_inter_recon_ex";
-    SO_TRY(check_geom(fn, H, W, bs, 0));
-    SO_TRY(check_qp(fn, qp));
-    SO_NEED(split, fn); SO_NEED(mv, fn); SO_NEED(qtc, fn); SO_NEED(out_recon, fn);
-    if (fme) SO_NEED(fme_planes, fn);
-    RefSet rs;
-    SO_TRY(make_refs(fn, refs, nref, &rs));
-    const size_t ps = so_fme_plane_stride(H, W);
-    hipStream_t st = (hipStream_t)stream;
-    if (fme)
-        for (int r = 0; r < nref; ++r)
-            SO_TRY(fme_planes_launch(refs[r], H, W, fme_wrap, fme_planes + (size_t)r * 4 * ps, ps, st));
-    return inter_recon_launch(rs, fme ? fme_planes : nullptr, ps, H, W, bs, qp, qp_row, qp_map, split, mv, qtc,
-                              out_recon, st);
+int so_encode_p_rows(const uint8_t* cur, const uint8_t* const* refs, int nref, int H, int W, int bs, int sr,
+                     int by0, int by1, int qp_rd, const int32_t* qp_row, int vbs, double lam, uint8_t* out_split,
+                     int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num,
+                     uint8_t* out_recon, int32_t* out_sse, int32_t* scratch, void* stream) {
+    return p_rows("so_encode_p_rows", cur, refs, nref, H, W, bs, sr, by0, by1, qp_rd, qp_row, nullptr, vbs, lam,
+                  SO_ME_FULL, 0, 0, nullptr, 0, out_split, out_mv, out_qtc, out_tokens, out_mae_num, out_recon, out_sse,
+                  scratch, stream);
 }
 
-int so_encode_i_rows_ex(const uint8_t* cur, int H, int W, int bs, int sr, int by0, int by1, int qp_rd,
-                        const int32_t* qp_row, const int32_t* qp_map, int vbs, double lam, uint8_t* out_split,
-                        int16_t* out_mv, int16_t* out_qtc, int32_t* out_tokens, int32_t* out_mae_num,
-                        uint8_t* out_recon, int32_t* out_sse, int32_t* scratch, void* stream) {
-    const char* fn = "so_encode_i_rows_ex";
-    SO_TRY(check_geom(fn, H, W, bs, vbs));
-    SO_TRY(check_intra_width(fn, W));
-    SO_TRY(check_sr(fn, sr));
-    SO_TRY(check_qp(fn, qp_rd));
-    SO_TRY(check_rows(fn, H, bs, by0, by1));
-    SO_NEED(cur, fn); SO_NEED(out_split, fn); SO_NEED(out_mv, fn); SO_NEED(out_qtc, fn);
-    SO_NEED(out_tokens, fn); SO_NEED(out_mae_num, fn); SO_NEED(out_recon, fn); SO_NEED(scratch, fn);
-    return intra_encode_launch(cur, H, W, bs, sr, by0, by1, qp_rd, qp_row, qp_map, vbs, lam, out_split, out_mv,
-                               out_qtc, out_tokens, out_mae_num, out_recon, out_sse, reinterpret_cast<uint8_t*>(scratch),
-                               (hipStream_t)stream);
-}
-
-int so_intra_recon_ex(int H, int W, int bs, int qp, const int32_t* qp_row, const int32_t* qp_map,
-                      const uint8_t* split, const int16_t* mv, const int16_t* qtc, uint8_t* out_recon,
-                      int32_t* scratch, void* stream) {
-    const char* fn = "so_intra_recon_ex";
-    SO_TRY(check_geom(fn, H, W, bs, 0));
-    SO_TRY(check_intra_width(fn, W));
-    SO_TRY(check_qp(fn, qp));
-    SO_NEED(split, fn); SO_NEED(mv, fn); SO_NEED(qtc, fn); SO_NEED(out_recon, fn); SO_NEED(scratch, fn);
-    return intra_recon_launch(H, W, bs, 64, qp, qp_row, qp_map, split, mv, qtc, out_recon,
-                              reinterpret_cast<uint8_t*>(scratch), (hipStream_t)stream);
+int so_encode_p_rows_ex(const uint8_t* cur, const uint8_t* const* refs, int nref, int H, int W, int bs, int sr,
+                        int by0, int by1, int qp_rd, const int32_t* qp_row, const int32_t* qp_map, int vbs, double lam,
+                        int me_mode, int fme, int fme_wrap, uint8_t* fme_planes, int flags, uint8_t* out_split, int16_t* out_mv, int16_t* out_qtc,
+                        int32_t* out_tokens, int32_t* out_mae_num, uint8_t* out_recon, int32_t* out_sse,
+                        int32_t* scratch, void* stream) {
+    // with nothing of the _ex form asked for this is so_encode_p_rows, and reports under that name
+    const bool plain = me_mode == SO_ME_FULL && !fme && !qp_map && !(flags & (SO_REUSE_ME | SO_TOKENS_ONLY));
+    return p_rows(plain ? "so_encode_p_rows" : "so_encode_p_rows_ex", cur, refs, nref, H, W, bs, sr, by0, by1, qp_rd,
+                  qp_row, qp_map, vbs, lam, me_mode, fme, fme_wrap, fme_planes, flags, out_split, out_mv, out_qtc,
+                  out_tokens, out_mae_num, out_recon, out_sse, scratch, stream);
 }
 
 int so_qp_map(const int32_t* tokens, int H, int W, int bs, int by0, int by1, int qp_rd, const int32_t* qp_row,
@@ -1101,14 +940,9 @@ int so_qp_map(const int32_t* tokens, int H, int W, int bs, int by0, int by1, int
     }
     SO_TRY(check_rows(fn, H, bs, by0, by1));
     SO_NEED(out_qp_map, fn);
-    if (qp_lo < 0 || qp_hi > 20 || qp_lo > qp_hi) {
-        set_error("%s: QP clamp [%d, %d] outside [0, 20]", fn, qp_lo, qp_hi);
-        return SO_E_INVALID;
-    }
+    SO_TRY(check_qp_clamp(fn, qp_lo, qp_hi));
     if (by1 <= by0) return SO_OK;
-    hipLaunchKernelGGL(qp_map_kernel, dim3(by1 - by0), dim3(256), 0, (hipStream_t)stream, tokens, W / bs, by0, qp_rd,
-                       qp_row, roi, qp_lo, qp_hi, out_qp_map);
-    return check_launch("qp_map_kernel");
+    return qp_map_launch(tokens, W / bs, by0, by1, qp_rd, qp_row, roi, qp_lo, qp_hi, out_qp_map, (hipStream_t)stream);
 }
 
 int so_sum_i32_rows(const int32_t* const* rows, int n, int len, int64_t* out, void* stream) {
@@ -1121,15 +955,8 @@ int so_sum_i32_rows(const int32_t* const* rows, int n, int len, int64_t* out, vo
     SO_NEED(rows, fn); SO_NEED(out, fn);
     for (int i0 = 0; i0 < n; i0 += kSumMax) {
         const int m = n - i0 < kSumMax ? n - i0 : kSumMax;
-        SumArgs a{};
-        for (int i = 0; i < m; ++i) {
-            SO_NEED(rows[i0 + i], fn);
-            a.p[i] = rows[i0 + i];
-        }
-        hipLaunchKernelGGL(sum_rows_kernel, dim3(m), dim3(kSumThreads), 0, (hipStream_t)stream, a, len,
-                           reinterpret_cast<long long*>(out + i0));
-        const int rc = check_launch("sum_rows_kernel");
-        if (rc != SO_OK) return rc;
+        for (int i = 0; i < m; ++i) SO_NEED(rows[i0 + i], fn);
+        SO_TRY(sum_rows_launch(rows + i0, m, len, out + i0, (hipStream_t)stream));
     }
     return SO_OK;
 }
@@ -1145,12 +972,7 @@ int so_sse_u8(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* out_sse, 
         set_error("%s: planes must be 16-byte aligned", fn);
         return SO_E_INVALID;
     }
-    int64_t blocks = (n / 16 + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, n,
-                       reinterpret_cast<unsigned long long*>(out_sse));
-    return check_launch("sse_kernel");
+    return sse_launch(a, b, n, out_sse, (hipStream_t)stream);
 }
 
 // ---- SSIM (so_ssim.hip) -----------------------------------------------------------------------
@@ -1192,13 +1014,6 @@ int so_ssim_u8(const uint8_t* const* a, const uint8_t* const* b, int nframes, in
 
 // ---- colour conversion (so_colour.hip) ------------------------------------------------------------
 namespace {
-struct ColourSpan {
-    uintptr_t lo, hi;   // [lo, hi)
-    bool dst;
-    const char* what;
-    int frame;
-};
-
 // two h-row views of `row` bytes per row and one pitch: does a byte belong to both?
 bool colour_views_overlap(uintptr_t a, uintptr_t b, size_t pitch, size_t row, int h) {
     const uintptr_t d = a < b ? b - a : a - b;
@@ -1264,7 +1079,7 @@ int colour_alias(const char* fn, const uint8_t* const* rgb, const uint8_t* const
     const size_t view = (size_t)(g.h - 1) * g.pitch + row;
     const size_t ny = (size_t)g.Hp * g.Wp, nc = ny / 4;
     const int nviews = layout == SO_LAYOUT_HWC ? 1 : 3;
-    std::vector<ColourSpan> spans;
+    std::vector<Span> spans;
     spans.reserve((size_t)nframes * 6);
     for (int i = 0; i < nframes; ++i) {
         const uintptr_t py = reinterpret_cast<uintptr_t>(y[i]), pu = reinterpret_cast<uintptr_t>(u[i]),
@@ -1275,21 +1090,7 @@ int colour_alias(const char* fn, const uint8_t* const* rgb, const uint8_t* const
         for (int c = 0; c < nviews; ++c)
             spans.push_back({pr + c * g.plane, pr + c * g.plane + view, !forward, "rgb", i});
     }
-    std::sort(spans.begin(), spans.end(), [](const ColourSpan& a, const ColourSpan& b) { return a.lo < b.lo; });
-    // the furthest end so far of a source, of a destination, and which span it belongs to
-    const ColourSpan *far_src = nullptr, *far_dst = nullptr;
-    for (const ColourSpan& s : spans) {
-        const ColourSpan* hit = nullptr;
-        if (far_dst && s.lo < far_dst->hi && (!s.dst || forward)) hit = far_dst;   // inverse: dst vs dst below
-        if (!hit && s.dst && far_src && s.lo < far_src->hi) hit = far_src;
-        if (hit) {
-            set_error("%s: %s[%d] aliases %s[%d] (a destination overlaps a source or another destination)", fn,
-                      s.what, s.frame, hit->what, hit->frame);
-            return SO_E_INVALID;
-        }
-        const ColourSpan*& far = s.dst ? far_dst : far_src;
-        if (!far || s.hi > far->hi) far = &s;
-    }
+    SO_TRY(check_spans(fn, spans, forward));   // inverse: destination against destination below
     if (!forward) {
         // RGB destinations may interleave row by row (crops of one canvas): an exact test, pair by pair
         std::vector<uintptr_t> views;
@@ -1431,7 +1232,7 @@ int so_scale_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const ui
     uint8_t* const* dsts[3] = {dy, du, dv};
     static const char* const sname[3] = {"sy", "su", "sv"};
     static const char* const dname[3] = {"dy", "du", "dv"};
-    std::vector<ColourSpan> spans;
+    std::vector<Span> spans;
     spans.reserve((size_t)nframes * 6);
     for (int i = 0; i < nframes; ++i)
         for (int k = 0; k < g.nplanes; ++k) {
@@ -1444,19 +1245,7 @@ int so_scale_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const ui
             spans.push_back({ps, ps + (size_t)(p.hs - 1) * p.spitch + p.ws, false, sname[k], i});
             spans.push_back({pd, pd + (size_t)p.Hp * p.Wp, true, dname[k], i});
         }
-    std::sort(spans.begin(), spans.end(), [](const ColourSpan& a, const ColourSpan& b) { return a.lo < b.lo; });
-    const ColourSpan *far_src = nullptr, *far_dst = nullptr;   // the furthest end so far of each kind
-    for (const ColourSpan& s : spans) {
-        const ColourSpan* hit = far_dst && s.lo < far_dst->hi ? far_dst
-                                : s.dst && far_src && s.lo < far_src->hi ? far_src : nullptr;
-        if (hit) {
-            set_error("%s: %s[%d] aliases %s[%d] (a destination overlaps a source or another destination)", fn,
-                      s.what, s.frame, hit->what, hit->frame);
-            return SO_E_INVALID;
-        }
-        const ColourSpan*& far = s.dst ? far_dst : far_src;
-        if (!far || s.hi > far->hi) far = &s;
-    }
+    SO_TRY(check_spans(fn, spans, true));
 
     for (int f0 = 0; f0 < nframes; f0 += kScaleBatch) {
         const int m = nframes - f0 < kScaleBatch ? nframes - f0 : kScaleBatch;
@@ -1576,11 +1365,8 @@ int so_pack_frames(int nframes, const int32_t* frame_types, const uint8_t* const
     return so_pack_frames_ex(nframes, frame_types, split, mv, qtc, nb, bs, offs, out, cap, nullptr, stream);
 }
 
-// validation and launch of both codings of the stream (bits: so_packbits.hip)
-static int pack_frames_any(const char* fn, bool bits, int nframes, const int32_t* frame_types,
-                           const uint8_t* const* split, const int16_t* const* mv, const int16_t* const* qtc, int nb,
-                           int bs, uint32_t* const* offs, uint8_t* const* out, unsigned long long cap,
-                           uint32_t* totals, void* stream) {
+// the block size and counts of every pack / unpack entry point (chroma passes its fixed 16)
+static int check_pack_counts(const char* fn, int bs, int nb, int nframes) {
     if (bs != 16 && bs != 8) {
         set_error("%s: block_size %d not built", fn, bs);
         return SO_E_UNSUPPORTED;
@@ -1589,6 +1375,15 @@ static int pack_frames_any(const char* fn, bool bits, int nframes, const int32_t
         set_error("%s: nb %d / nframes %d", fn, nb, nframes);
         return SO_E_INVALID;
     }
+    return SO_OK;
+}
+
+// validation and launch of both codings of the stream (bits: so_packbits.hip)
+static int pack_frames_any(const char* fn, bool bits, int nframes, const int32_t* frame_types,
+                           const uint8_t* const* split, const int16_t* const* mv, const int16_t* const* qtc, int nb,
+                           int bs, uint32_t* const* offs, uint8_t* const* out, unsigned long long cap,
+                           uint32_t* totals, void* stream) {
+    SO_TRY(check_pack_counts(fn, bs, nb, nframes));
     if (nframes == 0) return SO_OK;
     SO_NEED(frame_types, fn); SO_NEED(split, fn); SO_NEED(mv, fn); SO_NEED(qtc, fn); SO_NEED(offs, fn); SO_NEED(out, fn);
     std::vector<PackFrame> fr((size_t)nframes);
@@ -1608,14 +1403,7 @@ static int unpack_frames_any(const char* fn, bool bits, int nframes, const int32
                              const uint8_t* const* packed, const uint32_t* const* offs, int nb, int bs,
                              uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc, int32_t* err,
                              void* stream) {
-    if (bs != 16 && bs != 8) {
-        set_error("%s: block_size %d not built", fn, bs);
-        return SO_E_UNSUPPORTED;
-    }
-    if (nb <= 0 || nframes < 0) {
-        set_error("%s: nb %d / nframes %d", fn, nb, nframes);
-        return SO_E_INVALID;
-    }
+    SO_TRY(check_pack_counts(fn, bs, nb, nframes));
     if (nframes == 0) return SO_OK;
     SO_NEED(frame_types, fn); SO_NEED(packed, fn); SO_NEED(offs, fn); SO_NEED(split, fn); SO_NEED(mv, fn);
     SO_NEED(qtc, fn); SO_NEED(err, fn);
@@ -1674,10 +1462,7 @@ static int pack_chroma_any(const char* fn, bool bits, int nframes, const int16_t
                            const int16_t* const* qtc_v, int nb, uint32_t* const* offs, uint8_t* const* out,
                            bool after, const uint32_t* const* base, unsigned long long cap, uint32_t* totals,
                            void* stream) {
-    if (nb <= 0 || nframes < 0) {
-        set_error("%s: nb %d / nframes %d", fn, nb, nframes);
-        return SO_E_INVALID;
-    }
+    SO_TRY(check_pack_counts(fn, 16, nb, nframes));
     if (nframes == 0) return SO_OK;
     SO_NEED(qtc_u, fn); SO_NEED(qtc_v, fn); SO_NEED(offs, fn); SO_NEED(out, fn);
     if (after) SO_NEED(base, fn);
@@ -1693,10 +1478,7 @@ static int pack_chroma_any(const char* fn, bool bits, int nframes, const int16_t
 static int unpack_chroma_any(const char* fn, bool bits, int nframes, const uint8_t* const* packed,
                              const uint32_t* const* offs, int nb, int16_t* const* qtc_u, int16_t* const* qtc_v,
                              int32_t* err, void* stream) {
-    if (nb <= 0 || nframes < 0) {
-        set_error("%s: nb %d / nframes %d", fn, nb, nframes);
-        return SO_E_INVALID;
-    }
+    SO_TRY(check_pack_counts(fn, 16, nb, nframes));
     if (nframes == 0) return SO_OK;
     SO_NEED(packed, fn); SO_NEED(offs, fn); SO_NEED(qtc_u, fn); SO_NEED(qtc_v, fn); SO_NEED(err, fn);
     std::vector<ChromaUnpackFrame> fr((size_t)nframes);

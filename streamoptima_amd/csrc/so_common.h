@@ -26,6 +26,22 @@ inline int check_launch(const char* what) {
     return SO_OK;
 }
 
+// In a function that returns a status: leave with the first failing check's code ...
+#define SO_TRY(x)                     \
+    do {                              \
+        int _rc = (x);                \
+        if (_rc != SO_OK) return _rc; \
+    } while (0)
+
+// ... and refuse a NULL argument under the name it has at the call site
+#define SO_NEED(p, fn)                           \
+    do {                                         \
+        if (!(p)) {                              \
+            set_error("%s: %s is NULL", fn, #p); \
+            return SO_E_INVALID;                 \
+        }                                        \
+    } while (0)
+
 // Maximum reference frames carried in a kernel argument (nRefFrames, Encoder.py:24).
 constexpr int kMaxRef = SO_MAX_REF;
 

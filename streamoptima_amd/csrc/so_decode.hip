@@ -293,14 +293,6 @@ static int check_run(const char* fn, int nframes, int coding, int H, int W, int 
     return SO_OK;
 }
 
-#define SO_NEED(p, fn)                               \
-    do {                                             \
-        if (!(p)) {                                  \
-            set_error("%s: %s is NULL", fn, #p);     \
-            return SO_E_INVALID;                     \
-        }                                            \
-    } while (0)
-
 // the last `n` planes of `list` as a RefSet, the unused entries repeating the first (never indexed:
 // the kernels check or clamp the index against n)
 static RefSet ref_set(const std::vector<const uint8_t*>& list, int n) {

@@ -23,6 +23,7 @@
 // with FME the stride-2 sample of F at (X+dx, Y+dy) is 4 CONSECUTIVE bytes of phase plane
 // P_ab (a = (Y+dy) & 1, b = (X+dx) & 1), see so_me.hip FmePhase.
 #include "so_common.h"
+#include "so_launch.h"
 #include "so_dpp.h"
 
 namespace so {

@@ -14,6 +14,7 @@
 // intra_recon_kernel resolves those copy chains in parallel (pointer jumping), the
 // dequant/IDCT having been done for all blocks in parallel.
 #include "so_block.h"
+#include "so_launch.h"
 
 namespace so {
 

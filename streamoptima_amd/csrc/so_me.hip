@@ -29,6 +29,7 @@
 #include "so_block.h"
 #include "so_common.h"
 #include "so_dpp.h"
+#include "so_launch.h"
 #include "so_run.h"
 
 namespace so {

@@ -15,6 +15,7 @@
 // A second kernel adds a frame's partials in a fixed order and divides by the window count:
 // no floating-point atomics, the same bits from run to run and for any batching.
 #include "so_common.h"
+#include "so_launch.h"
 
 #pragma clang fp contract(off)   // an identical pair must give exactly 1.0 (no FMA on one side only)
 

@@ -11,6 +11,7 @@
 // workgroup carries 16 blocks.  Everything between the HBM reads (cur, pred, ME result)
 // and the HBM writes (QTC, recon, symbols) stays in VGPRs / LDS.
 #include "so_block.h"
+#include "so_launch.h"
 
 namespace so {
 

@@ -12,7 +12,6 @@ import collections
 import contextlib
 from dataclasses import dataclass, field
 
-import ctypes
 import os
 
 import torch
@@ -54,9 +53,7 @@ def ssim_planes(lib, device, a_planes, b_planes, h: int, w: int, win: int, out, 
                 raise ValueError(f"ssim: {name} planes must be uint8 2-D tensors of at least {h}x{w} on {ws.device} "
                                  "with contiguous rows and one row stride")
         pitches.append(int(planes[0].stride(0)))
-    pa = (ctypes.c_void_p * n)(*[t.data_ptr() for t in a_planes])
-    pb = (ctypes.c_void_p * n)(*[t.data_ptr() for t in b_planes])
-    rc = lib.so_ssim_u8(pa, pb, n, int(h), int(w), pitches[0], pitches[1], int(win), out.data_ptr(), ws.data_ptr(),
+    rc = lib.so_ssim_u8(_lib.ptr_array(a_planes), _lib.ptr_array(b_planes), n, int(h), int(w), pitches[0], pitches[1], int(win), out.data_ptr(), ws.data_ptr(),
                         _lib.stream_handle(device))
     _lib.check(rc, "so_ssim_u8")
     return out
@@ -257,6 +254,33 @@ class Engine:
                             sse=torch.zeros(max(nbs, (by1 - by0) * bs), dtype=torch.int32, device=d),
                             extra={"by0": by0, "by1": by1})
 
+    @staticmethod
+    def out_arrays(outs: list) -> tuple:
+        """The seven per-frame output pointer arrays of the run entry points, in argument order
+        (split, mv, qtc, tokens, mae_num, recon, sse), for a list of FrameSymbols."""
+        return tuple(_lib.ptr_array([getattr(o, k) for o in outs])
+                     for k in ("split", "mv", "qtc", "tokens", "mae_num", "recon", "sse"))
+
+    @staticmethod
+    def _stamp(outs: list, frame_type: int, qp_rd: int, qp_row) -> None:
+        """What the encode calls record on the symbols they filled."""
+        for o in outs:
+            o.frame_type, o.qp_rd = frame_type, int(qp_rd)
+            o.qp_row = None if qp_row is None else list(qp_row)
+
+    def _check_offs(self, offs: list, what: str) -> None:
+        for o in offs:
+            if o.dtype != torch.int32 or o.numel() != self.nb + 1 or not o.is_contiguous():
+                raise ValueError(f"{what}: offs must be contiguous int32 [{self.nb + 1}]")
+
+    def _run_workspace(self) -> torch.Tensor:
+        """The persistent runs' workspace, allocated on first use."""
+        if getattr(self, "_run_ws", None) is None:
+            # the timeout count (RUN_TIMEOUT_WORD) is zeroed here once and then only by check_run
+            self._run_ws = torch.zeros(self.lib.so_p_run_workspace_elems(self.h, self.w), dtype=torch.int32,
+                                       device=self.device)
+        return self._run_ws
+
     def encode_p_rows(self, cur, refs, by0: int, by1: int, qp_rd: int, out: FrameSymbols,
                       qp_row_dev: torch.Tensor | None = None, fme_wrap: bool = True,
                       qp_map_dev: torch.Tensor | None = None, reuse_me: bool = False, qp_row=None,
@@ -284,8 +308,7 @@ class Engine:
                 out.split.data_ptr(), out.mv.data_ptr(), out.qtc.data_ptr(), out.tokens.data_ptr(),
                 out.mae_num.data_ptr(), out.recon.data_ptr(), _lib.ptr(out.sse), self.scratch.data_ptr(), st)
             _lib.check(rc, "so_encode_p_rows_ex")
-        out.frame_type, out.qp_rd = 1, int(qp_rd)
-        out.qp_row = None if qp_row is None else list(qp_row)
+        self._stamp([out], 1, qp_rd, qp_row)
         return out
 
     # ---- P-frame runs (one persistent launch) ----------------------------------------------
@@ -311,25 +334,14 @@ class Engine:
         qrd = qp_row_dev if qp_row_dev is not None else self.qp_row_tensor(qp_row)
         for t, name in [(ref0, "ref0")] + [(c, "cur") for c in curs]:
             self._check_plane(t, name)
-        if getattr(self, "_run_ws", None) is None:
-            # the timeout count (RUN_TIMEOUT_WORD) is zeroed here once and then only by check_run
-            self._run_ws = torch.zeros(self.lib.so_p_run_workspace_elems(self.h, self.w), dtype=torch.int32,
-                                       device=self.device)
-
-        def arr(ts):
-            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        ws = self._run_workspace()
         with self._zero_skip_option():
             rc = self.lib.so_encode_p_run(
-                arr(curs), n, ref0.data_ptr(), self.h, self.w, self.bs, self.sr, int(qp_rd), _lib.ptr(qrd),
-                int(self.vbs), self.lam,
-                arr([o.split for o in outs]), arr([o.mv for o in outs]), arr([o.qtc for o in outs]),
-                arr([o.tokens for o in outs]), arr([o.mae_num for o in outs]), arr([o.recon for o in outs]),
-                arr([o.sse for o in outs]), self._run_ws.data_ptr(), _lib.stream_handle(self.device))
+                _lib.ptr_array(curs), n, ref0.data_ptr(), self.h, self.w, self.bs, self.sr, int(qp_rd), _lib.ptr(qrd),
+                int(self.vbs), self.lam, *self.out_arrays(outs), ws.data_ptr(), _lib.stream_handle(self.device))
         _lib.check(rc, "so_encode_p_run")
         self._last_run_outs = list(outs)
-        for o in outs:
-            o.frame_type, o.qp_rd = 1, int(qp_rd)
-            o.qp_row = None if qp_row is None else list(qp_row)
+        self._stamp(outs, 1, qp_rd, qp_row)
         return outs
 
     def encode_p_run_2pass(self, curs: list, ref0: torch.Tensor, qp_rd: int, outs: list, qp_maps: list,
@@ -351,22 +363,13 @@ class Engine:
         for m in qp_maps:
             if m.dtype != torch.int32 or m.numel() != self.nb or m.device != self.device or not m.is_contiguous():
                 raise ValueError(f"qp_maps entries must be contiguous int32 [{self.nb}] on {self.device}")
-        if getattr(self, "_run_ws", None) is None:
-            self._run_ws = torch.zeros(self.lib.so_p_run_workspace_elems(self.h, self.w), dtype=torch.int32,
-                                       device=self.device)
-
-        def arr(ts):
-            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
         rc = self.lib.so_encode_p_run_2pass(
-            arr(curs), n, ref0.data_ptr(), self.h, self.w, self.bs, self.sr, int(qp_rd), _lib.ptr(qrd),
-            _lib.ptr(roi_dev), int(qp_lo), int(qp_hi),
-            arr([o.split for o in outs]), arr([o.mv for o in outs]), arr([o.qtc for o in outs]),
-            arr([o.tokens for o in outs]), arr([o.mae_num for o in outs]), arr([o.recon for o in outs]),
-            arr([o.sse for o in outs]), arr(qp_maps), self._run_ws.data_ptr(), _lib.stream_handle(self.device))
+            _lib.ptr_array(curs), n, ref0.data_ptr(), self.h, self.w, self.bs, self.sr, int(qp_rd), _lib.ptr(qrd),
+            _lib.ptr(roi_dev), int(qp_lo), int(qp_hi), *self.out_arrays(outs), _lib.ptr_array(qp_maps),
+            self._run_workspace().data_ptr(), _lib.stream_handle(self.device))
         _lib.check(rc, "so_encode_p_run_2pass")
+        self._stamp(outs, 1, qp_rd, qp_row)
         for o, m in zip(outs, qp_maps):
-            o.frame_type, o.qp_rd = 1, int(qp_rd)
-            o.qp_row = None if qp_row is None else list(qp_row)
             o.extra["qp_map"] = m
         return outs
 
@@ -396,24 +399,15 @@ class Engine:
         n = len(curs)
         if n == 0:
             return []
-        if getattr(self, "_run_ws", None) is None:
-            self._run_ws = torch.zeros(self.lib.so_p_run_workspace_elems(self.h, self.w), dtype=torch.int32,
-                                       device=self.device)
-
-        def arr(ts):
-            return (ctypes.c_void_p * n)(*[0 if t is None else t.data_ptr() for t in ts])
+        ws = self._run_workspace()
         with self._zero_skip_option():
             rc = self.lib.so_encode_p_runs(
-                arr(curs), n, arr(refs), (ctypes.c_int32 * n)(*ref_frame), self.h, self.w, self.bs, self.sr,
-                int(qp_rd), _lib.ptr(qrd), int(self.vbs), self.lam, arr([o.split for o in outs]),
-                arr([o.mv for o in outs]), arr([o.qtc for o in outs]), arr([o.tokens for o in outs]),
-                arr([o.mae_num for o in outs]), arr([o.recon for o in outs]), arr([o.sse for o in outs]),
-                self._run_ws.data_ptr(), _lib.stream_handle(self.device))
+                _lib.ptr_array(curs), n, _lib.ptr_array(refs), _lib.i32_array(ref_frame), self.h, self.w, self.bs,
+                self.sr, int(qp_rd), _lib.ptr(qrd), int(self.vbs), self.lam, *self.out_arrays(outs), ws.data_ptr(),
+                _lib.stream_handle(self.device))
         _lib.check(rc, "so_encode_p_runs")
         self._last_run_outs = list(outs)
-        for o in outs:
-            o.frame_type, o.qp_rd = 1, int(qp_rd)
-            o.qp_row = None if qp_row is None else list(qp_row)
+        self._stamp(outs, 1, qp_rd, qp_row)
         return [r[2] for r in runs]
 
     def run_timed_out(self) -> bool:
@@ -501,8 +495,7 @@ class Engine:
             out.qtc.data_ptr(), out.tokens.data_ptr(), out.mae_num.data_ptr(), out.recon.data_ptr(),
             _lib.ptr(out.sse), self.scratch.data_ptr(), _lib.stream_handle(self.device))
         _lib.check(rc, "so_encode_i_rows_ex")
-        out.frame_type, out.qp_rd = 0, int(qp_rd)
-        out.qp_row = None if qp_row is None else list(qp_row)
+        self._stamp([out], 0, qp_rd, qp_row)
         return out
 
     # ---- decode ---------------------------------------------------------------------------
@@ -634,10 +627,7 @@ class Engine:
         out = torch.empty((n, cap), dtype=torch.uint8, device=self.device) if out is None else out
         if offs.shape != (n, nb + 1) or offs.dtype != torch.int32 or out.shape[0] != n or out.dtype != torch.uint8:
             raise ValueError("pack_symbols: offs must be int32 [n, nb + 1] and out uint8 [n, cap]")
-
-        def arr(ts):
-            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-        types = (ctypes.c_int32 * n)(*[int(s.frame_type) for s in syms])
+        arr, types = _lib.ptr_array, _lib.i32_array([s.frame_type for s in syms])
         pack = self.lib.so_pack_frames_bits if bits else self.lib.so_pack_frames_ex
         rc = pack(n, types, arr([s.split for s in syms]), arr([s.mv for s in syms]),
                   arr([s.qtc for s in syms]), nb, self.bs, arr(list(offs)), arr(list(out)),
@@ -654,10 +644,7 @@ class Engine:
         n = len(packed)
         syms = [self.new_symbols(int(t)) for t in frame_types]
         err = torch.zeros(1, dtype=torch.int32, device=self.device)
-
-        def arr(ts):
-            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
-        types = (ctypes.c_int32 * n)(*[int(t) for t in frame_types])
+        arr, types = _lib.ptr_array, _lib.i32_array(frame_types)
         rc = getattr(self.lib, name)(n, types, arr(packed), arr(offs), self.nb, self.bs, arr([s.split for s in syms]),
                                      arr([s.mv for s in syms]), arr([s.qtc for s in syms]), err.data_ptr(),
                                      _lib.stream_handle(self.device))
@@ -718,9 +705,7 @@ class Engine:
         if totals is not None and totals_ptr is not None:
             raise ValueError("pack_chroma_symbols: totals or totals_ptr, not both")
         tot = _lib.ptr(totals) if totals_ptr is None else int(totals_ptr)
-
-        def arr(ts):
-            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        arr = _lib.ptr_array
         name = "so_pack_chroma_frames_bits" if bits else "so_pack_chroma_frames"
         base = ()
         if after is not None:
@@ -741,14 +726,10 @@ class Engine:
         n = len(packed)
         if n == 0 or len(offs) != n:
             raise ValueError("unpack_chroma_symbols: one offsets tensor per packed stream, at least one")
-        for o in offs:
-            if o.dtype != torch.int32 or o.numel() != self.nb + 1 or not o.is_contiguous():
-                raise ValueError(f"unpack_chroma_symbols: offs must be contiguous int32 [{self.nb + 1}]")
+        self._check_offs(offs, "unpack_chroma_symbols")
         q = torch.empty((n, 2, self.nb, 64), dtype=torch.int16, device=self.device)
         err = torch.zeros(1, dtype=torch.int32, device=self.device)
-
-        def arr(ts):
-            return (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        arr = _lib.ptr_array
         rc = getattr(self.lib, name)(n, arr(packed), arr(offs), self.nb, arr([q[i, 0] for i in range(n)]),
                                      arr([q[i, 1] for i in range(n)]), err.data_ptr(),
                                      _lib.stream_handle(self.device))
@@ -775,7 +756,7 @@ class Engine:
         for t in ts:
             if t is not None and (t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous()):
                 raise ValueError(f"{what}: a contiguous int32 tensor on {self.device}")
-        return (ctypes.c_void_p * n)(*[_lib.ptr(t) for t in ts]), ts
+        return _lib.ptr_array(ts), ts
 
     def decode_p_frames(self, packed: list, offs: list, refs0: list, nref_max: int, qp: int, qp_rows=None,
                         qp_maps=None, coding: str = "varint", out_split=None, out_mv=None, out_recon=None,
@@ -792,9 +773,7 @@ class Engine:
         n = len(packed)
         if len(offs) != n or n == 0:
             raise ValueError("decode_p_frames: one offsets tensor per packed stream, at least one")
-        for o in offs:
-            if o.dtype != torch.int32 or o.numel() != self.nb + 1 or not o.is_contiguous():
-                raise ValueError(f"decode_p_frames: offs must be contiguous int32 [{self.nb + 1}]")
+        self._check_offs(offs, "decode_p_frames")
         for k, r in enumerate(refs0):
             self._check_plane(r, f"refs0[{k}]")
         d = self.device
@@ -808,9 +787,7 @@ class Engine:
             raise ValueError(f"decode_p_frames: err must be a contiguous int32 [{n}] on {d}")
         qr, keep_r = self._qp_ptrs(qp_rows, n, "decode_p_frames qp_rows")
         qm, keep_m = self._qp_ptrs(qp_maps, n, "decode_p_frames qp_maps")
-
-        def arr(ts):
-            return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+        arr = _lib.ptr_array
         rc = self.lib.so_decode_p_frames(n, self._coding_number(coding), arr(packed), arr(offs), self.h, self.w,
                                          self.bs, int(qp), qr, qm, arr(refs0) if refs0 else None, len(refs0),
                                          int(nref_max), arr(out_split), arr(out_mv), arr(out_recon), err.data_ptr(),
@@ -830,9 +807,7 @@ class Engine:
         n = len(packed)
         if n == 0 or len(offs) != n or len(frame_types) != n or len(split) != n or len(mv) != n:
             raise ValueError("decode_chroma_frames: one entry per frame in every list, at least one frame")
-        for o in offs:
-            if o.dtype != torch.int32 or o.numel() != self.nb + 1 or not o.is_contiguous():
-                raise ValueError(f"decode_chroma_frames: offs must be contiguous int32 [{self.nb + 1}]")
+        self._check_offs(offs, "decode_chroma_frames")
         if len(refs0_u) != len(refs0_v):
             raise ValueError(f"chroma: {len(refs0_u)} U references against {len(refs0_v)} V references")
         for k, (ru, rv) in enumerate(zip(refs0_u, refs0_v)):
@@ -850,10 +825,7 @@ class Engine:
             raise ValueError(f"decode_chroma_frames: err must be a contiguous int32 [{n}] on {d}")
         qr, keep_r = self._qp_ptrs(qp_rows, n, "decode_chroma_frames qp_rows")
         qm, keep_m = self._qp_ptrs(qp_maps, n, "decode_chroma_frames qp_maps")
-
-        def arr(ts):
-            return (ctypes.c_void_p * len(ts))(*[_lib.ptr(t) for t in ts])
-        types = (ctypes.c_int32 * n)(*[int(t) for t in frame_types])
+        arr, types = _lib.ptr_array, _lib.i32_array(frame_types)
         rc = self.lib.so_decode_chroma_frames(n, self._coding_number(coding), types, arr(packed), arr(offs), self.h,
                                               self.w, self.bs, arr(split), arr(mv), int(qp), qr, qm, int(qp_offset),
                                               arr(refs0_u) if refs0_u else None, arr(refs0_v) if refs0_v else None,
@@ -870,8 +842,7 @@ class Engine:
         if any(r.numel() != length or r.dtype != torch.int32 or not r.is_contiguous() for r in rows):
             raise ValueError("sum_rows: contiguous int32 tensors of one length")
         out = torch.empty(n, dtype=torch.int64, device=self.device) if out is None else out
-        ptrs = (ctypes.c_void_p * max(n, 1))(*[r.data_ptr() for r in rows])
-        rc = self.lib.so_sum_i32_rows(ptrs, n, length, out.data_ptr(), _lib.stream_handle(self.device))
+        rc = self.lib.so_sum_i32_rows(_lib.ptr_array(rows), n, length, out.data_ptr(), _lib.stream_handle(self.device))
         _lib.check(rc, "so_sum_i32_rows")
         return out
 

@@ -241,15 +241,13 @@ class StripeRunRank:
             while j < nf and j % intra_dur != 0:
                 j += 1
             n = j - i
-            arr = lambda xs: (ctypes.c_void_p * n)(*xs)  # noqa: E731
             ss = syms[i:j]
+            split, mv, qtc, tokens, mae_num, _, sse = e.out_arrays(ss)
+            # the reconstructions are the stripe's virtual full-frame bases, not the symbols' tensors
+            recon = (ctypes.c_void_p * n)(*[self.virt(k) for k in range(i, j)])
             _lib.check(lib.so_encode_p_run_stripe(
-                arr([frames[k].data_ptr() for k in range(i, j)]), n, self.virt(i - 1), e.h, e.w, e.bs, e.sr,
-                self.by0, self.by1, int(qp), None,
-                arr([s.split.data_ptr() for s in ss]), arr([s.mv.data_ptr() for s in ss]),
-                arr([s.qtc.data_ptr() for s in ss]), arr([s.tokens.data_ptr() for s in ss]),
-                arr([s.mae_num.data_ptr() for s in ss]), arr([self.virt(k) for k in range(i, j)]),
-                arr([s.sse.data_ptr() for s in ss]), self._ws.data_ptr(), i,
+                _lib.ptr_array([frames[k] for k in range(i, j)]), n, self.virt(i - 1), e.h, e.w, e.bs, e.sr,
+                self.by0, self.by1, int(qp), None, split, mv, qtc, tokens, mae_num, recon, sse, self._ws.data_ptr(), i,
                 up_v, dn_v, self.stride, my_up, my_dn, up_f, dn_f, ep, int(self.max_wg), st), "so_encode_p_run_stripe")
             for s in ss:
                 s.frame_type, s.qp_rd = 1, int(qp)
@@ -547,20 +545,16 @@ class FramePipeRank:
         if ks:
             n = len(ks)
             slot0 = plan["slot0"]
-            arr = lambda xs: (ctypes.c_void_p * n)(*xs)  # noqa: E731
             ss = [syms[k] for k in ks]
             p2planes, p2flags = self.peer2
-            outs = (arr([s.split.data_ptr() for s in ss]), arr([s.mv.data_ptr() for s in ss]),
-                    arr([s.qtc.data_ptr() for s in ss]), arr([s.tokens.data_ptr() for s in ss]),
-                    arr([s.mae_num.data_ptr() for s in ss]), arr([s.recon.data_ptr() for s in ss]),
-                    arr([s.sse.data_ptr() for s in ss]))
+            outs = e.out_arrays(ss)
             land = (self._planes.value, self._flags.value, slot0, pplanes, pflags, p2planes, p2flags,
-                    (ctypes.c_int32 * n)(*plan["push"]), self.nslots, self.stride, ep, int(self.max_wg))
-            curs = arr([frames[k].data_ptr() for k in ks])
+                    _lib.i32_array(plan["push"]), self.nslots, self.stride, ep, int(self.max_wg))
+            curs = _lib.ptr_array([frames[k] for k in ks])
             if two_pass:
                 _lib.check(lib.so_encode_p_run_fpipe_2pass(
                     curs, n, e.h, e.w, e.bs, e.sr, int(qp), _lib.ptr(qrd), _lib.ptr(roi_dev), int(qp_clamp[0]),
-                    int(qp_clamp[1]), *outs, arr([s.extra["qp_map"].data_ptr() for s in ss]), self._ws.data_ptr(),
+                    int(qp_clamp[1]), *outs, _lib.ptr_array([s.extra["qp_map"] for s in ss]), self._ws.data_ptr(),
                     *land, self.p2lag, st), "so_encode_p_run_fpipe_2pass")
             else:
                 _lib.check(lib.so_encode_p_run_fpipe2(curs, n, e.h, e.w, e.bs, e.sr, int(qp), _lib.ptr(qrd), int(e.vbs),
