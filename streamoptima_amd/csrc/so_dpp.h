@@ -65,6 +65,29 @@ SO_DEV uint64_t wave_min_u64_dpp(uint64_t v) {
 
 SO_DEV uint64_t wave_min_u64(uint64_t v) { return wave_min_u64_dpp(v); }
 
+// wave_min_u32 / wave_min_u64_dpp of a value that is already the same in every lane of each
+// aligned group of UNI lanes (4: a DPP quad, 16: a row): the steps inside a group would compare
+// a value with itself, so a quad-uniform value starts at row_half_mirror (which pairs quads 0, 1
+// and 2, 3 of a row) and a row-uniform one at row_bcast15.
+template <int UNI>
+SO_DEV uint32_t wave_min_u32_uni(uint32_t v) {
+    static_assert(UNI == 4 || UNI == 16, "quad- or row-uniform");
+    if constexpr (UNI == 4) {
+        v = __builtin_elementwise_min(v, (uint32_t)__builtin_amdgcn_update_dpp(~0u, v, kDppHalfMirror, 0xF, 0xF, false));
+        v = __builtin_elementwise_min(v, (uint32_t)__builtin_amdgcn_update_dpp(~0u, v, kDppMirror, 0xF, 0xF, false));
+    }
+    v = __builtin_elementwise_min(v, (uint32_t)__builtin_amdgcn_update_dpp(~0u, v, kDppBcast15, 0xA, 0xF, false));
+    v = __builtin_elementwise_min(v, (uint32_t)__builtin_amdgcn_update_dpp(~0u, v, kDppBcast31, 0xC, 0xF, false));
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+template <int UNI>
+SO_DEV uint64_t wave_min_u64_uni(uint64_t v) {
+    const uint32_t hi = wave_min_u32_uni<UNI>((uint32_t)(v >> 32));
+    const uint32_t lo = wave_min_u32_uni<UNI>((uint32_t)(v >> 32) == hi ? (uint32_t)v : ~0u);
+    return ((uint64_t)hi << 32) | lo;
+}
+
 // inclusive prefix sum over the wave (lane i: v_0 + ... + v_i): row_shr 1, 2, 4, 8 inside each
 // 16-lane row, then row_bcast15 / row_bcast31 carry the row totals into the rows above
 SO_DEV uint32_t wave_incl_scan_u32(uint32_t v) {

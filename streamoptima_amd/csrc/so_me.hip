@@ -678,9 +678,11 @@ struct Sea2GeoT {
 using Sea2Geo = Sea2GeoT<8>;
 
 // 4 bytes of window row `row` starting at byte column `col` (single copy, pitch RP dwords)
-template <int RP>
+// M24: the row's offset by a 24-bit multiply (sea2_tile: a full 32-bit one issues at a quarter
+// of the rate, and the compiler cannot see that a lane-derived row is small)
+template <int RP, bool M24 = false>
 SO_DEV uint32_t win_u32(const uint32_t* win, int row, int col) {
-    lds_vu32p p = (lds_vu32p)(win + row * RP + (col >> 2));
+    lds_vu32p p = (lds_vu32p)(win + (M24 ? __mul24(row, RP) : row * RP) + (col >> 2));
     return __builtin_amdgcn_alignbyte(p[1], p[0], (uint32_t)(col & 3));
 }
 
@@ -1331,10 +1333,11 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             if (bx0 + bxl >= nbx || byt0 + byl >= by1) continue;   // wave-uniform
             const int x = x0 + bxl * 16, y = y0 + byl * 16;
             // the co-located block's vector in the previous frame (issued now, used after the bounds)
-            uint32_t pmv = 0x80008000u;   // (-32768, -32768): no hint
+            // (held in a vector register until then: read into a scalar one here, the wave waits
+            // for the load before it starts the bounds)
+            uint32_t pmv_v = 0x80008000u;   // (-32768, -32768): no hint
             if (!VBS && prev_mv != nullptr && r == 0)
-                pmv = __builtin_amdgcn_readfirstlane(
-                    *reinterpret_cast<const uint32_t*>(prev_mv + ((size_t)(byt0 + byl - by0) * nbx + bx0 + bxl) * 12));
+                pmv_v = *reinterpret_cast<const uint32_t*>(prev_mv + ((size_t)(byt0 + byl - by0) * nbx + bx0 + bxl) * 12);
             if constexpr (VBS) {
                 if (x != 0 && y != 0) {   // uniform: block + sub-block search
                     if (x + 48 <= W && y + 48 <= H && sea_vbs_block<G>(L, u, bxl, byl, tid, ballot_lists)) continue;
@@ -1358,7 +1361,11 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             for (int j = 0; j < 4; ++j) A[j] = a4[u * 4 + j];
             // ---- 1. lower bounds --------------------------------------------------------------
             const int cB = bxl * 16 + xi;
-            const int lb0 = (byl * 16 + 16 * hh) * B4P + (cB & 3) * G::WD + (cB >> 2);   // byte offset
+            // (lane-derived factors through 24-bit multiplies, here and below: see win_u32; the block
+            // row's offset is opaque because folded into hh's factor it is a 32-bit multiply again)
+            int lbrow = byl * 16 * B4P;
+            asm volatile("" : "+s"(lbrow));
+            const int lb0 = lbrow + __mul24(hh, 16 * B4P) + __mul24(cB & 3, G::WD) + (cB >> 2);   // byte offset
             const uint32_t bsh = (uint32_t)lb0 & 3;
             int lo1 = lb0 >> 2;
             asm volatile("" : "+v"(lo1));
@@ -1397,7 +1404,7 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             }
             uint32_t lb2 = 0;
             {
-                int lo2 = ((byl * 16 + d2) * B4P + ((bxl * 16 + 32) >> 2)) >> 2;
+                int lo2 = (lbrow + __mul24(d2, B4P) + ((bxl * 16 + 32) >> 2)) >> 2;
                 asm volatile("" : "+v"(lo2));
                 lds_vu32p p2 = (lds_vu32p)(b4w + lo2);
 #pragma unroll
@@ -1437,17 +1444,18 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             // 16-bit halves (each <= 65,280).  The previous frame's vector is close to the minimum
             // for most blocks; with it a 4K bench P-frame leaves 9.5 instead of 15.9 survivors per
             // block, 0.18 % instead of 1.4 % past the cap (tests/analysis/sea_u_sources.py)
+            const uint32_t pmv = __builtin_amdgcn_readfirstlane(pmv_v);
             const int pdx = (int)(int16_t)(pmv & 0xFFFFu), pdy = (int)pmv >> 16;
             const bool pv = pdx >= -SR && pdx <= SR && pdy >= -SR && pdy <= SR && x + pdx >= 0 && x + pdx < W - 16 &&
                             y + pdy >= 0 && y + pdy < H - 16;   // uniform
             uint32_t U;
             {
                 const int row = lane >> 2, kk = lane & 3;
-                const uint32_t c = curt[crow0 + row * G::CPD + kk];
-                const uint32_t w = win_u32<RP>(win, byl * 16 + cdi + row, bxl * 16 + cdx + 4 * kk);
+                const uint32_t c = curt[crow0 + __mul24(row, G::CPD) + kk];
+                const uint32_t w = win_u32<RP, true>(win, byl * 16 + cdi + row, bxl * 16 + cdx + 4 * kk);
                 uint32_t sp = __builtin_amdgcn_sad_u8(c, w, 0u);
                 if (pv) {
-                    const uint32_t wp = win_u32<RP>(win, byl * 16 + SR + pdy + row, bxl * 16 + SR + pdx + 4 * kk);
+                    const uint32_t wp = win_u32<RP, true>(win, byl * 16 + SR + pdy + row, bxl * 16 + SR + pdx + 4 * kk);
                     sp = __builtin_amdgcn_sad_hi_u8(c, wp, sp);
                 }
                 const uint32_t both = wave_sum_u32(sp);
@@ -1519,6 +1527,16 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             uint64_t best = kNoKey;
+            // me_key of a survivor: |dx| + |dy| is one v_sad_u16 of (dxi << 16 | di) against
+            // (16, 16), and the low word is put together in 32 bits
+            const uint32_t rkey = (uint32_t)r << 16;
+            // code / 33 for a 16-bit code, as a 24-bit multiply whatever the compiler knows of
+            // the code's range (it is exact for every code < 65,536)
+            const auto code_dxi = [](int cand) -> int { return (int)(((uint32_t)cand & 0xFFFFu) * 0xF83Fu >> 21); };
+            const auto cand_key = [&](uint32_t sad, int dxi, int di, int cand) -> uint64_t {
+                const uint32_t l1 = __builtin_amdgcn_sad_u16(((uint32_t)dxi << 16) | (uint32_t)di, 0x00100010u, 0u);
+                return ((uint64_t)sad << 32) | (uint64_t)((l1 << 24) | rkey | (uint32_t)cand);
+            };
             if (nsur <= 4) {
                 // one pass: 16 lanes (one DPP row) per survivor, a row per lane
                 SO_MARK(sur_le4);
@@ -1527,9 +1545,9 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
                 const uint32_t c0 = cr_[0], c1 = cr_[1], c2 = cr_[2], c3 = cr_[3];
                 const bool act = (uint32_t)sidx < nsur;
                 const int cand = act ? (int)mylist[sidx] : cs;
-                const int dxi = cand / 33, di = cand - dxi * 33;
+                const int dxi = code_dxi(cand), di = cand - dxi * 33;
                 const int col = bxl * 16 + dxi;
-                int wo = (byl * 16 + di + row) * RP + (col >> 2);
+                int wo = __mul24(byl * 16 + di + row, RP) + (col >> 2);
                 asm volatile("" : "+v"(wo));
                 lds_vu32p p = (lds_vu32p)(win + wo);
                 const uint32_t sh = (uint32_t)(col & 3);
@@ -1539,10 +1557,9 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
                 sad = __builtin_amdgcn_sad_u8(c2, __builtin_amdgcn_alignbyte(q3, q2, sh), sad);
                 sad = __builtin_amdgcn_sad_u8(c3, __builtin_amdgcn_alignbyte(q4, q3, sh), sad);
                 sad = row_sum_u32(sad);
-                const int dx = dxi - 16, dy = di - 16;
-                const uint64_t key = me_key(sad, (uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)),
-                                            (uint32_t)r, (uint32_t)cand);
-                best = (act && key < best) ? key : best;
+                asm volatile("" : "+v"(sad));   // the sum's last DPP add stays one instruction, outside the select
+                best = act ? cand_key(sad, dxi, di, cand) : best;
+                best = wave_min_u64_uni<16>(best);   // one key per row
             } else {
                 // four lanes (one DPP quad) per survivor, rows 4q..4q+3 per lane: sixteen
                 // survivors per pass (one survivor per lane left 3/4 of the lanes idle at the
@@ -1558,10 +1575,10 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
                     SO_MARK(sur_pass);
                     const bool act = s0 + (uint32_t)sidx < nsur;
                     const int cand = act ? (int)mylist[s0 + sidx] : cs;
-                    const int dxi = cand / 33, di = cand - dxi * 33;
+                    const int dxi = code_dxi(cand), di = cand - dxi * 33;
                     const int col = bxl * 16 + dxi;
                     const uint32_t sh = (uint32_t)(col & 3);
-                    int wo = (byl * 16 + di + 4 * q) * RP + (col >> 2);
+                    int wo = __mul24(byl * 16 + di + 4 * q, RP) + (col >> 2);
                     asm volatile("" : "+v"(wo));
                     uint32_t sad = 0;
 #pragma unroll
@@ -1574,13 +1591,11 @@ SO_DEV void sea2_tile(const Sea2Lds& L, int tile, const uint8_t* __restrict__ cu
                         sad = __builtin_amdgcn_sad_u8(cr[rr][3], __builtin_amdgcn_alignbyte(q4, q3, sh), sad);
                     }
                     sad = quad_sum_u32(sad);
-                    const int dx = dxi - 16, dy = di - 16;
-                    const uint64_t key = me_key(sad, (uint32_t)((dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)),
-                                                (uint32_t)r, (uint32_t)cand);
+                    const uint64_t key = cand_key(sad, dxi, di, cand);
                     best = (act && key < best) ? key : best;
                 }
+                best = wave_min_u64_uni<4>(best);   // one key per quad
             }
-            best = wave_min_u64_dpp(best);
             if (lane == 0 && best < keys[u]) keys[u] = best;
         }
     }
