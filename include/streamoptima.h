@@ -618,6 +618,21 @@ int so_ssim_u8(const uint8_t* const* a, const uint8_t* const* b, int nframes, in
  * outside 1..SO_MAX_REF on a P-frame, a NULL required pointer or a reconstruction that aliases a
  * reference (or the other reconstruction) is SO_E_INVALID, before any launch.
  * so_chroma_recon_frame is the decoder: the same prediction and inverse path from qtc_u / qtc_v.
+ *
+ * so_chroma_encode_frame_ex / so_chroma_recon_frame_ex take one more argument, mv_frac_bits = s: the
+ * number of fractional bits of the luma vector seen from the chroma plane -- 1 when the luma vectors
+ * are full-sample (the two functions above, which forward with 1 and report under their own names),
+ * 2 when they are half-sample (FMEEnable).  Only the P-frame prediction depends on it.  With
+ * D = 1 << s, for the sample at (X, Y) with vector (dx, dy, r):
+ *     ix = dx >> s (arithmetic, floor)      fx = dx & (D - 1)         iy, fy alike
+ *     x0 = clamp(X + ix, 0, W/2 - 1)        x1 = clamp(X + ix + (fx != 0), 0, W/2 - 1)      y0, y1 alike
+ *     P  = ((D-fx)(D-fy) R[y0][x0] + fx (D-fy) R[y0][x1] + (D-fx) fy R[y1][x0] + fx fy R[y1][x1]
+ *           + (1 << (2s - 1))) >> 2s
+ * on the chroma plane R of reference clamp(r, 0, nref - 1).  Exact integers; the weights sum to D^2,
+ * so P is in 0..255, and the clamps keep it total for any int16 vector.  At s = 1 (fx, fy in {0, 1})
+ * the weights are 4, 2 + 2 or 1 + 1 + 1 + 1 over 4 and x1 = clamp(X + ix + fx): the formula above, bit
+ * for bit.  A multiple of D moves whole samples.  mv_frac_bits other than 1 / 2 is SO_E_INVALID
+ * before any launch (checked after bs); every other rule is that of the base function.
  */
 int so_chroma_encode_frame(const uint8_t* cur_u, const uint8_t* cur_v, const uint8_t* const* refs_u,
                            const uint8_t* const* refs_v, int nref, int H, int W, int bs, int frame_type,
@@ -629,6 +644,17 @@ int so_chroma_recon_frame(const uint8_t* const* refs_u, const uint8_t* const* re
                           int bs, int frame_type, const uint8_t* split, const int16_t* mv, int qp,
                           const int32_t* qp_row, const int32_t* qp_map, int qp_offset, const int16_t* qtc_u,
                           const int16_t* qtc_v, uint8_t* out_recon_u, uint8_t* out_recon_v, void* stream);
+int so_chroma_encode_frame_ex(const uint8_t* cur_u, const uint8_t* cur_v, const uint8_t* const* refs_u,
+                              const uint8_t* const* refs_v, int nref, int H, int W, int bs, int frame_type,
+                              const uint8_t* split, const int16_t* mv, int qp, const int32_t* qp_row,
+                              const int32_t* qp_map, int qp_offset, int16_t* out_qtc_u, int16_t* out_qtc_v,
+                              int32_t* out_tokens, uint8_t* out_recon_u, uint8_t* out_recon_v,
+                              int32_t* out_sse, int mv_frac_bits, void* stream);
+int so_chroma_recon_frame_ex(const uint8_t* const* refs_u, const uint8_t* const* refs_v, int nref, int H,
+                             int W, int bs, int frame_type, const uint8_t* split, const int16_t* mv, int qp,
+                             const int32_t* qp_row, const int32_t* qp_map, int qp_offset,
+                             const int16_t* qtc_u, const int16_t* qtc_v, uint8_t* out_recon_u,
+                             uint8_t* out_recon_v, int mv_frac_bits, void* stream);
 
 /*
  * Colour conversion (build extension; DESIGN.md "Colour conversion"): 8-bit RGB to and from the
@@ -981,6 +1007,9 @@ int so_unpack_chroma_frames_bits(int nframes, const uint8_t* const* packed,
  *   other than 0 / 1, qp_offset outside -20..20, nref0 outside 0..nref_max, a P-frame whose list
  *   is empty, planes that are not 8-byte aligned, an out_recon_u[i] equal to out_recon_v[i], or a
  *   reconstruction that aliases a refs0 plane or another reconstruction.
+ *   so_decode_chroma_frames_ex adds mv_frac_bits as so_chroma_recon_frame_ex takes it (mv[i] then
+ *   being the half-sample vectors of a luma frame decoded under FME); so_decode_chroma_frames
+ *   forwards with 1 under its own name.  A value other than 1 / 2 is SO_E_INVALID, checked after bs.
  */
 int so_decode_p_frames(int nframes, int coding, const uint8_t* const* packed,
                        const uint32_t* const* offs, int H, int W, int bs, int qp,
@@ -996,6 +1025,14 @@ int so_decode_chroma_frames(int nframes, int coding, const int32_t* frame_types,
                             const uint8_t* const* refs0_v, int nref0, int nref_max,
                             uint8_t* const* out_recon_u, uint8_t* const* out_recon_v, int32_t* err,
                             void* stream);
+int so_decode_chroma_frames_ex(int nframes, int coding, const int32_t* frame_types,
+                               const uint8_t* const* packed, const uint32_t* const* offs, int H, int W,
+                               int bs, const uint8_t* const* split, const int16_t* const* mv, int qp,
+                               const int32_t* const* qp_row, const int32_t* const* qp_map,
+                               int qp_offset, const uint8_t* const* refs0_u,
+                               const uint8_t* const* refs0_v, int nref0, int nref_max,
+                               uint8_t* const* out_recon_u, uint8_t* const* out_recon_v, int32_t* err,
+                               int mv_frac_bits, void* stream);
 
 #ifdef __cplusplus
 }

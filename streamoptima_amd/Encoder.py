@@ -53,8 +53,9 @@ class Y_Video_codec(BlockAPI):
                  lam=None, VBSEnable=False, nRefFrames=1, yuv_file=None, y_only_frame_arr=None,
                  fast_me=False, FMEEnable=False, RCFlag=None, targetBR=None, frame_rate=30,
                  qp_rate_tables=None, intra_thresh=None, ParallelMode=0, device=None, roi=None, qp_clamp=(0, 12),
-                 ssim=False, chroma=False, chroma_qp_offset=0, uv_frame_arr=None, rgb_frame_arr=None, colour=None):
-        if chroma and FMEEnable:
+                 ssim=False, chroma=False, chroma_qp_offset=0, uv_frame_arr=None, rgb_frame_arr=None, colour=None,
+                 chroma_subpel=False):
+        if chroma and FMEEnable and not chroma_subpel:
             raise NotImplementedError("chroma with FMEEnable is not built: the luma MVs are in half-pel units there")
         if chroma and block_size != 16:
             raise NotImplementedError(f"chroma needs block_size 16 (8x8 chroma blocks), got {block_size}")
@@ -106,7 +107,7 @@ class Y_Video_codec(BlockAPI):
         self.decoder = _decoder_mod.decoder(intra_mode, intra_dur, block_size, frames, h_pixels, w_pixels, Qp,
                                             nRefFrames, FMEEnable, lam, VBSEnable, False, RCFlag, targetBR,
                                             frame_rate, qp_rate_tables, ParallelMode=ParallelMode,
-                                            device=self.device)
+                                            device=self.device, chroma_subpel=chroma_subpel)
         if yuv_file is not None:
             self.y_only_f_arr = self.read_yuv(yuv_file, h_pixels, w_pixels, frames)
         else:
@@ -126,6 +127,9 @@ class Y_Video_codec(BlockAPI):
         # planes of yuv_file.  Off (default) nothing is allocated and no launch is added.
         self.chroma = bool(chroma)
         self.chroma_qp_offset = int(chroma_qp_offset)
+        # chroma_subpel=True lets chroma follow FMEEnable: the half-sample luma vectors predict U and V
+        # at quarter-sample positions (so_chroma_encode_frame_ex).  Without FMEEnable it changes nothing.
+        self.chroma_subpel = bool(chroma_subpel)
         self.uv_f_arr = None
         if self.chroma:
             if yuv_file is not None and uv_frame_arr is None:
@@ -278,7 +282,8 @@ class Y_Video_codec(BlockAPI):
         hp, wp = self._geometry()
         if self._engine is None or (self._engine.h, self._engine.w) != (hp, wp):
             self._engine = Engine(hp, wp, self.block_size, self.search_range, self.VBSEnable, self.lam,
-                                  self.device, me_mode=self._me_mode(), fme=bool(self.FMEEnable))
+                                  self.device, me_mode=self._me_mode(), fme=bool(self.FMEEnable),
+                                  chroma_subpel=self.chroma_subpel)
         return self._engine
 
     def _me_mode(self) -> int:

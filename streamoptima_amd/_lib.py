@@ -62,6 +62,10 @@ _SIGS = {
     "so_chroma_encode_frame": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp], _i),
     "so_chroma_recon_frame": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "so_chroma_encode_frame_ex": ([_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _i, _vp], _i),
+    "so_chroma_recon_frame_ex": ([_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i,
+                                  _vp], _i),
     "so_rgb_to_yuv420": ([_vp, _i, _i, _i, _i, _sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "so_yuv420_to_rgb": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _sz, _vp], _i),
     "so_scale_yuv420": ([_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _i, _i, _i, _i,
@@ -105,6 +109,8 @@ _SIGS = {
     "so_decode_p_frames": ([_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "so_decode_chroma_frames": ([_i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i,
                                  _vp, _vp, _vp, _vp], _i),
+    "so_decode_chroma_frames_ex": ([_i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i,
+                                    _vp, _vp, _vp, _i, _vp], _i),
     "so_fme_plane_stride": ([_i, _i], _sz),
     "so_fme_workspace_bytes": ([_i, _i, _i], _sz),
     "so_fme_planes": ([_vp, _i, _i, _i, _vp, _vp], _i),

@@ -1261,15 +1261,19 @@ int so_scale_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const ui
 }
 
 // ---- chroma 4:2:0 (so_chroma.hip) ----------------------------------------------------------------
+// so_chroma_encode_frame / so_chroma_recon_frame and their _ex forms: one function, the base
+// names passing mv_frac_bits 1 under their own name
 static int chroma_frame(const char* fn, bool encode, const uint8_t* cur_u, const uint8_t* cur_v,
                         const uint8_t* const* refs_u, const uint8_t* const* refs_v, int nref, int H, int W, int bs,
                         int frame_type, const uint8_t* split, const int16_t* mv, int qp, const int32_t* qp_row,
                         const int32_t* qp_map, int qp_offset, int16_t* qtc_u, int16_t* qtc_v, int32_t* out_tokens,
-                        uint8_t* out_recon_u, uint8_t* out_recon_v, int32_t* out_sse, void* stream) {
+                        uint8_t* out_recon_u, uint8_t* out_recon_v, int32_t* out_sse, int mv_frac_bits,
+                        void* stream) {
     if (bs != 16) {
         set_error("%s: block_size %d not built (chroma follows 16x16 luma blocks)", fn, bs);
         return SO_E_UNSUPPORTED;
     }
+    SO_TRY(check_mv_frac_bits(fn, mv_frac_bits));
     if (H <= 0 || W <= 0 || H % 16 || W % 16) {
         set_error("%s: luma frame %dx%d must be a positive multiple of 16 (pad with pad_hw)", fn, W, H);
         return SO_E_INVALID;
@@ -1330,6 +1334,7 @@ static int chroma_frame(const char* fn, bool encode, const uint8_t* cur_u, const
     a.split = split; a.mv = mv;
     a.qp = qp; a.qp_row = qp_row; a.qp_map = qp_map; a.qp_offset = qp_offset;
     a.tokens = out_tokens; a.sse = out_sse;
+    a.mv_frac_bits = mv_frac_bits;
     return chroma_launch(a, encode, (hipStream_t)stream);
 }
 
@@ -1341,7 +1346,18 @@ int so_chroma_encode_frame(const uint8_t* cur_u, const uint8_t* cur_v, const uin
                            void* stream) {
     return chroma_frame("so_chroma_encode_frame", true, cur_u, cur_v, refs_u, refs_v, nref, H, W, bs, frame_type,
                         split, mv, qp, qp_row, qp_map, qp_offset, out_qtc_u, out_qtc_v, out_tokens, out_recon_u,
-                        out_recon_v, out_sse, stream);
+                        out_recon_v, out_sse, 1, stream);
+}
+
+int so_chroma_encode_frame_ex(const uint8_t* cur_u, const uint8_t* cur_v, const uint8_t* const* refs_u,
+                              const uint8_t* const* refs_v, int nref, int H, int W, int bs, int frame_type,
+                              const uint8_t* split, const int16_t* mv, int qp, const int32_t* qp_row,
+                              const int32_t* qp_map, int qp_offset, int16_t* out_qtc_u, int16_t* out_qtc_v,
+                              int32_t* out_tokens, uint8_t* out_recon_u, uint8_t* out_recon_v, int32_t* out_sse,
+                              int mv_frac_bits, void* stream) {
+    return chroma_frame("so_chroma_encode_frame_ex", true, cur_u, cur_v, refs_u, refs_v, nref, H, W, bs, frame_type,
+                        split, mv, qp, qp_row, qp_map, qp_offset, out_qtc_u, out_qtc_v, out_tokens, out_recon_u,
+                        out_recon_v, out_sse, mv_frac_bits, stream);
 }
 
 int so_chroma_recon_frame(const uint8_t* const* refs_u, const uint8_t* const* refs_v, int nref, int H, int W, int bs,
@@ -1350,7 +1366,17 @@ int so_chroma_recon_frame(const uint8_t* const* refs_u, const uint8_t* const* re
                           uint8_t* out_recon_u, uint8_t* out_recon_v, void* stream) {
     return chroma_frame("so_chroma_recon_frame", false, nullptr, nullptr, refs_u, refs_v, nref, H, W, bs, frame_type,
                         split, mv, qp, qp_row, qp_map, qp_offset, const_cast<int16_t*>(qtc_u),
-                        const_cast<int16_t*>(qtc_v), nullptr, out_recon_u, out_recon_v, nullptr, stream);
+                        const_cast<int16_t*>(qtc_v), nullptr, out_recon_u, out_recon_v, nullptr, 1, stream);
+}
+
+int so_chroma_recon_frame_ex(const uint8_t* const* refs_u, const uint8_t* const* refs_v, int nref, int H, int W,
+                             int bs, int frame_type, const uint8_t* split, const int16_t* mv, int qp,
+                             const int32_t* qp_row, const int32_t* qp_map, int qp_offset, const int16_t* qtc_u,
+                             const int16_t* qtc_v, uint8_t* out_recon_u, uint8_t* out_recon_v, int mv_frac_bits,
+                             void* stream) {
+    return chroma_frame("so_chroma_recon_frame_ex", false, nullptr, nullptr, refs_u, refs_v, nref, H, W, bs,
+                        frame_type, split, mv, qp, qp_row, qp_map, qp_offset, const_cast<int16_t*>(qtc_u),
+                        const_cast<int16_t*>(qtc_v), nullptr, out_recon_u, out_recon_v, nullptr, mv_frac_bits, stream);
 }
 
 // ---- packed symbol stream (so_pack.hip) -----------------------------------------------------

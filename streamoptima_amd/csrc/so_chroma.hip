@@ -8,13 +8,16 @@
 //               quadrant when the luma block is split -- halved: ix = dx >> 1, fx = dx & 1,
 //               P = (R[y0][x0] + R[y0][x1] + R[y1][x0] + R[y1][x1] + 2) >> 2 with
 //               x0 = clamp(X + ix), x1 = clamp(X + ix + fx) (y alike) on the chroma
-//               reconstruction R of reference clamp(r, 0, nref - 1);
+//               reconstruction R of reference clamp(r, 0, nref - 1).  That is the case S = 1
+//               of chroma_pred4<S> (so_chroma.h); with half-sample luma vectors (FME,
+//               mv_frac_bits = 2) the S = 2 instantiation weights the four taps by the
+//               quarter-sample phase;
 //   transform   residual -> apply_2d_dct (Encoder.py:779) -> quantize_TC (:787) with
 //               generate_Q_matrix(8, qpc) (:938) -> len(entropy_encoder_block) (:1086) ->
 //               rescale_QTC (:820) -> apply_2d_idct (:810) -> (P + idct).astype(uint8) (:824);
 //   qpc         clamp(base + qp_offset, 0, 20), base = the block's QP-map entry, else its
 //               row's qp_row entry, else the frame QP.
-// One kernel template: ENC = true is the encoder (residual .. reconstruction, tokens, SSE),
+// One kernel template (x S): ENC = true is the encoder (residual .. reconstruction, tokens, SSE),
 // ENC = false the decoder (qtc -> reconstruction).  One launch covers both planes: task
 // t < nb is block t of U, t >= nb block t - nb of V.  8 lanes of a wavefront own a block
 // (lane l = block row l, so_block.h), 32 blocks per 256-thread workgroup, an 8 x 9 FP64 LDS
@@ -24,7 +27,7 @@
 
 namespace so {
 
-template <bool ENC>
+template <bool ENC, int S>
 __global__ void __launch_bounds__(256) chroma_kernel(const ChromaArgs a) {
     constexpr int N = 8, P = N + 1, G = 256 / N;
     __shared__ double lds[G * N * P];
@@ -50,7 +53,7 @@ __global__ void __launch_bounds__(256) chroma_kernel(const ChromaArgs a) {
         for (int h = 0; h < 2; ++h) {
             const int16_t* mq = m + 3 * (h ? q1 : q0);
             const int dx = mq[0], dy = mq[1], r = clampi(mq[2], 0, a.nref - 1);
-            chroma_pred4(pick_ref(pl.refs, r), a.Wc, a.Hc, X + 4 * h, Y, dx, dy, pred + 4 * h);
+            chroma_pred4<S>(pick_ref(pl.refs, r), a.Wc, a.Hc, X + 4 * h, Y, dx, dy, pred + 4 * h);
         }
     }
 
@@ -94,10 +97,16 @@ __global__ void __launch_bounds__(256) chroma_kernel(const ChromaArgs a) {
 
 int chroma_launch(const ChromaArgs& a, bool encode, hipStream_t st) {
     const dim3 grid((2 * a.nb + 31) / 32), blk(256);
-    if (encode)
-        hipLaunchKernelGGL(chroma_kernel<true>, grid, blk, 0, st, a);
-    else
-        hipLaunchKernelGGL(chroma_kernel<false>, grid, blk, 0, st, a);
+    if (a.mv_frac_bits == 2) {
+        if (encode)
+            hipLaunchKernelGGL((chroma_kernel<true, 2>), grid, blk, 0, st, a);
+        else
+            hipLaunchKernelGGL((chroma_kernel<false, 2>), grid, blk, 0, st, a);
+    } else if (encode) {
+        hipLaunchKernelGGL((chroma_kernel<true, 1>), grid, blk, 0, st, a);
+    } else {
+        hipLaunchKernelGGL((chroma_kernel<false, 1>), grid, blk, 0, st, a);
+    }
     return check_launch("chroma_kernel");
 }
 

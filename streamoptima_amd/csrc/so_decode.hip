@@ -198,7 +198,7 @@ struct DecodeChromaArgs {
 
 // A record holds U's and V's block: slot k of the tile is U at [0, 64), V at [64, 128).  Phase 2's
 // task t in [0, 128) is U of slot t (t < 64) or V of slot t - 64, 32 tasks a round.
-template <typename Reader>
+template <typename Reader, int S>
 __global__ void __launch_bounds__(256) decode_chroma_kernel(const DecodeChromaArgs a) {
     constexpr int N = 8, P = N + 1, GR = 256 / N, T = kDecodeTile, STRIDE = decode_tile_stride(128);
     static_assert((T * STRIDE) % 8 == 0 && (STRIDE * 2) % 16 == 0, "16-byte tile accesses");
@@ -253,7 +253,7 @@ __global__ void __launch_bounds__(256) decode_chroma_kernel(const DecodeChromaAr
             for (int h = 0; h < 2; ++h) {
                 const int16_t* mq = m + 3 * (h ? q1 : q0);
                 const int dx = mq[0], dy = mq[1], r = clampi(mq[2], 0, a.nref - 1);
-                chroma_pred4(pick_ref(a.refs[pi], r), a.Wc, a.Hc, X + 4 * h, Y, dx, dy, pred + 4 * h);
+                chroma_pred4<S>(pick_ref(a.refs[pi], r), a.Wc, a.Hc, X + 4 * h, Y, dx, dy, pred + 4 * h);
             }
         }
         int q[N];
@@ -363,18 +363,19 @@ extern "C" int so_decode_p_frames(int nframes, int coding, const uint8_t* const*
     return SO_OK;
 }
 
-extern "C" int so_decode_chroma_frames(int nframes, int coding, const int32_t* frame_types,
-                                       const uint8_t* const* packed, const uint32_t* const* offs, int H, int W, int bs,
-                                       const uint8_t* const* split, const int16_t* const* mv, int qp,
-                                       const int32_t* const* qp_row, const int32_t* const* qp_map, int qp_offset,
-                                       const uint8_t* const* refs0_u, const uint8_t* const* refs0_v, int nref0,
-                                       int nref_max, uint8_t* const* out_recon_u, uint8_t* const* out_recon_v,
-                                       int32_t* err, void* stream) {
-    const char* fn = "so_decode_chroma_frames";
+// so_decode_chroma_frames and its _ex form: the base name passes mv_frac_bits 1 under its own name
+static int decode_chroma_frames(const char* fn, int nframes, int coding, const int32_t* frame_types,
+                                const uint8_t* const* packed, const uint32_t* const* offs, int H, int W, int bs,
+                                const uint8_t* const* split, const int16_t* const* mv, int qp,
+                                const int32_t* const* qp_row, const int32_t* const* qp_map, int qp_offset,
+                                const uint8_t* const* refs0_u, const uint8_t* const* refs0_v, int nref0,
+                                int nref_max, uint8_t* const* out_recon_u, uint8_t* const* out_recon_v,
+                                int32_t* err, int mv_frac_bits, void* stream) {
     if (bs != 16) {
         set_error("%s: block_size %d not built (chroma follows 16x16 luma blocks)", fn, bs);
         return SO_E_UNSUPPORTED;
     }
+    SO_TRY(check_mv_frac_bits(fn, mv_frac_bits));
     const int rc = check_run(fn, nframes, coding, H, W, bs, qp, nref_max);
     if (rc != SO_OK) return rc;
     if (qp_offset < -20 || qp_offset > 20) {
@@ -456,10 +457,40 @@ extern "C" int so_decode_chroma_frames(int nframes, int coding, const int32_t* f
     for (int i = 0; i < nframes; ++i) {
         const DecodeChromaArgs& a = args[(size_t)i];
         const dim3 grid((a.nb + kDecodeTile - 1) / kDecodeTile), blk(256);
-        if (coding == 1) hipLaunchKernelGGL(decode_chroma_kernel<VarintReader>, grid, blk, 0, st, a);
-        else hipLaunchKernelGGL(decode_chroma_kernel<BitReader>, grid, blk, 0, st, a);
+        if (mv_frac_bits == 2) {
+            if (coding == 1) hipLaunchKernelGGL((decode_chroma_kernel<VarintReader, 2>), grid, blk, 0, st, a);
+            else hipLaunchKernelGGL((decode_chroma_kernel<BitReader, 2>), grid, blk, 0, st, a);
+        } else if (coding == 1) {
+            hipLaunchKernelGGL((decode_chroma_kernel<VarintReader, 1>), grid, blk, 0, st, a);
+        } else {
+            hipLaunchKernelGGL((decode_chroma_kernel<BitReader, 1>), grid, blk, 0, st, a);
+        }
         const int lrc = check_launch("decode_chroma_kernel");
         if (lrc != SO_OK) return lrc;
     }
     return SO_OK;
+}
+
+extern "C" int so_decode_chroma_frames(int nframes, int coding, const int32_t* frame_types,
+                                       const uint8_t* const* packed, const uint32_t* const* offs, int H, int W, int bs,
+                                       const uint8_t* const* split, const int16_t* const* mv, int qp,
+                                       const int32_t* const* qp_row, const int32_t* const* qp_map, int qp_offset,
+                                       const uint8_t* const* refs0_u, const uint8_t* const* refs0_v, int nref0,
+                                       int nref_max, uint8_t* const* out_recon_u, uint8_t* const* out_recon_v,
+                                       int32_t* err, void* stream) {
+    return decode_chroma_frames("so_decode_chroma_frames", nframes, coding, frame_types, packed, offs, H, W, bs, split,
+                                mv, qp, qp_row, qp_map, qp_offset, refs0_u, refs0_v, nref0, nref_max, out_recon_u,
+                                out_recon_v, err, 1, stream);
+}
+
+extern "C" int so_decode_chroma_frames_ex(int nframes, int coding, const int32_t* frame_types,
+                                          const uint8_t* const* packed, const uint32_t* const* offs, int H, int W,
+                                          int bs, const uint8_t* const* split, const int16_t* const* mv, int qp,
+                                          const int32_t* const* qp_row, const int32_t* const* qp_map, int qp_offset,
+                                          const uint8_t* const* refs0_u, const uint8_t* const* refs0_v, int nref0,
+                                          int nref_max, uint8_t* const* out_recon_u, uint8_t* const* out_recon_v,
+                                          int32_t* err, int mv_frac_bits, void* stream) {
+    return decode_chroma_frames("so_decode_chroma_frames_ex", nframes, coding, frame_types, packed, offs, H, W, bs,
+                                split, mv, qp, qp_row, qp_map, qp_offset, refs0_u, refs0_v, nref0, nref_max,
+                                out_recon_u, out_recon_v, err, mv_frac_bits, stream);
 }

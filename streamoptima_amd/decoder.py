@@ -38,7 +38,7 @@ def _canon_frame(frame_type, mvs, residuals, bs):
 class decoder:
     def __init__(self, intra_mode, intra_dur, block_size, frames, height, width, Qp, nRefFrames, FMEEnable, lam,
                  VBSEnable, VBSoverlay=None, RCFlag=None, targetBR=None, frame_rate=30, qp_rate_tables=None,
-                 ParallelMode=0, device=None):
+                 ParallelMode=0, device=None, chroma_subpel=False):
         self.intra_mode = intra_mode
         self.intra_dur = intra_dur
         self.block_size = block_size
@@ -52,6 +52,10 @@ class decoder:
         self.Qp = Qp
         self.nRefFrames = nRefFrames
         self.FMEEnable = FMEEnable
+        # build extension: with FMEEnable, read the half-sample luma vectors as quarter-sample chroma
+        # vectors (DESIGN.md "Chroma with FMEEnable").  Like FMEEnable itself the precision is not in any
+        # file: it is this argument, and it must be what the encoder was given
+        self.chroma_subpel = bool(chroma_subpel)
         self.lam = lam
         self.VBSEnable = VBSEnable
         self.VBSoverlay = VBSoverlay
@@ -71,7 +75,8 @@ class decoder:
         hp = -(-self.h_pixels // bs) * bs
         wp = -(-self.w_pixels // bs) * bs
         if self._engine is None:
-            self._engine = Engine(hp, wp, bs, 16, False, 0.0, self.device, fme=bool(self.FMEEnable))
+            self._engine = Engine(hp, wp, bs, 16, False, 0.0, self.device, fme=bool(self.FMEEnable),
+                                  chroma_subpel=self.chroma_subpel)
         return self._engine
 
     def _rc(self):
@@ -169,7 +174,7 @@ class decoder:
         """U and V of every frame from the package's per-frame lists: mv_file as decode() takes
         it (the luma motion), chroma_residuals[i] = (qtc_u, qtc_v) as int16 [nb, 64] arrays or the
         package's "chroma approx residual" entry.  Returns per-frame (U, V) cropped to the picture."""
-        if self.FMEEnable:
+        if self.FMEEnable and not self.chroma_subpel:
             raise NotImplementedError("chroma with FMEEnable is not built")
         if self.block_size != 16:
             raise NotImplementedError("chroma needs block_size 16")
@@ -279,7 +284,7 @@ class decoder:
         if (meta["h"], meta["w"], meta["bs"], meta["nb"]) != (eng.h, eng.w, eng.bs, eng.nb):
             raise ValueError(f"{path}: {meta['w']}x{meta['h']} bs {meta['bs']} does not match this decoder")
         chroma = meta["chroma_packed"] is not None
-        if chroma and self.FMEEnable:
+        if chroma and self.FMEEnable and not self.chroma_subpel:
             raise NotImplementedError("chroma with FMEEnable is not built")
         if chroma and self.block_size != 16:
             raise NotImplementedError("chroma needs block_size 16")

@@ -99,7 +99,8 @@ class Engine:
     """Kernels for one frame geometry on one device."""
 
     def __init__(self, height: int, width: int, block_size: int = 16, search_range: int = 16,
-                 vbs: bool = False, lam: float | None = None, device=None, me_mode: int = 0, fme: bool = False):
+                 vbs: bool = False, lam: float | None = None, device=None, me_mode: int = 0, fme: bool = False,
+                 chroma_subpel: bool = False):
         if height % block_size or width % block_size:
             raise ValueError(f"frame {width}x{height} is not a multiple of block_size {block_size}")
         self.h, self.w, self.bs, self.sr = height, width, block_size, search_range
@@ -119,6 +120,8 @@ class Engine:
         # ME variant (include/streamoptima.h SO_ME_*): fast_me / FMEEnable
         self.me_mode = int(me_mode)
         self.fme = bool(fme)
+        # chroma under FME: the half-sample luma vectors as quarter-sample chroma vectors (opt-in)
+        self.chroma_subpel = bool(chroma_subpel)
         self._fme_ws = None
         self._consts: collections.OrderedDict = collections.OrderedDict()   # device_const_i32 (LRU)
         self._pinned_consts: set = set()                                    # ... held by captured graphs
@@ -538,8 +541,9 @@ class Engine:
             raise ValueError(f"{name} must be a contiguous uint8 {hc}x{wc} tensor on {self.device}")
 
     def _chroma_args(self, sym: FrameSymbols, refs_u: list, refs_v: list):
-        """The luma frame's part of a chroma call: references, motion and the QP source."""
-        if self.fme:
+        """The luma frame's part of a chroma call: references, motion and the QP source.  Under
+        FME, which chroma_subpel has to allow, the callers pass mv_frac_bits 2 to the _ex entry points."""
+        if self.fme and not self.chroma_subpel:
             raise NotImplementedError("chroma with FMEEnable: the luma MVs are in half-pel units")
         inter = int(sym.frame_type) == 1
         if inter:
@@ -570,6 +574,14 @@ class Engine:
         self._check_chroma_plane(cur_v, "cur_v")
         args = self._chroma_args(sym, refs_u, refs_v)
         out = out if out is not None and out.tokens is not None else self.new_chroma_symbols()
+        if self.fme:   # with chroma_subpel (_chroma_args refused otherwise): half-sample luma vectors
+            rc = self.lib.so_chroma_encode_frame_ex(cur_u.data_ptr(), cur_v.data_ptr(), *args, int(qp_offset),
+                                                    out.qtc_u.data_ptr(), out.qtc_v.data_ptr(), out.tokens.data_ptr(),
+                                                    out.recon_u.data_ptr(), out.recon_v.data_ptr(),
+                                                    out.sse.data_ptr(), 2, _lib.stream_handle(self.device))
+            _lib.check(rc, "so_chroma_encode_frame_ex")
+            out.frame_type, out.qp_offset = int(sym.frame_type), int(qp_offset)
+            return out
         rc = self.lib.so_chroma_encode_frame(cur_u.data_ptr(), cur_v.data_ptr(), *args, int(qp_offset),
                                              out.qtc_u.data_ptr(), out.qtc_v.data_ptr(), out.tokens.data_ptr(),
                                              out.recon_u.data_ptr(), out.recon_v.data_ptr(), out.sse.data_ptr(),
@@ -593,10 +605,16 @@ class Engine:
             out = ChromaSymbols(int(sym.frame_type), qtc_u, qtc_v, rec[0], rec[1])
         else:
             out.qtc_u, out.qtc_v, out.tokens, out.sse = qtc_u, qtc_v, None, None
-        rc = self.lib.so_chroma_recon_frame(*args, int(qp_offset), qtc_u.data_ptr(), qtc_v.data_ptr(),
-                                            out.recon_u.data_ptr(), out.recon_v.data_ptr(),
-                                            _lib.stream_handle(self.device))
-        _lib.check(rc, "so_chroma_recon_frame")
+        if self.fme:
+            rc = self.lib.so_chroma_recon_frame_ex(*args, int(qp_offset), qtc_u.data_ptr(), qtc_v.data_ptr(),
+                                                   out.recon_u.data_ptr(), out.recon_v.data_ptr(), 2,
+                                                   _lib.stream_handle(self.device))
+            _lib.check(rc, "so_chroma_recon_frame_ex")
+        else:
+            rc = self.lib.so_chroma_recon_frame(*args, int(qp_offset), qtc_u.data_ptr(), qtc_v.data_ptr(),
+                                                out.recon_u.data_ptr(), out.recon_v.data_ptr(),
+                                                _lib.stream_handle(self.device))
+            _lib.check(rc, "so_chroma_recon_frame")
         out.frame_type, out.qp_offset = int(sym.frame_type), int(qp_offset)
         return out
 
@@ -801,8 +819,9 @@ class Engine:
         """so_decode_chroma_frames: U and V of a run of frames from their packed chroma records and
         the frames' luma split / mv (None for an I-frame).  The reference lists start as refs0_u /
         refs0_v, are cleared by an I-frame, take every reconstruction and hold at most nref_max
-        planes.  Other arguments as decode_p_frames.  Returns (recon_u, recon_v, err)."""
-        if self.fme:
+        planes.  Other arguments as decode_p_frames.  Returns (recon_u, recon_v, err).  Under FME
+        with chroma_subpel the mv are the half-sample luma vectors (so_decode_chroma_frames_ex)."""
+        if self.fme and not self.chroma_subpel:
             raise NotImplementedError("chroma with FMEEnable: the luma MVs are in half-pel units")
         n = len(packed)
         if n == 0 or len(offs) != n or len(frame_types) != n or len(split) != n or len(mv) != n:
@@ -826,12 +845,15 @@ class Engine:
         qr, keep_r = self._qp_ptrs(qp_rows, n, "decode_chroma_frames qp_rows")
         qm, keep_m = self._qp_ptrs(qp_maps, n, "decode_chroma_frames qp_maps")
         arr, types = _lib.ptr_array, _lib.i32_array(frame_types)
-        rc = self.lib.so_decode_chroma_frames(n, self._coding_number(coding), types, arr(packed), arr(offs), self.h,
-                                              self.w, self.bs, arr(split), arr(mv), int(qp), qr, qm, int(qp_offset),
-                                              arr(refs0_u) if refs0_u else None, arr(refs0_v) if refs0_v else None,
-                                              len(refs0_u), int(nref_max), arr(out_u), arr(out_v), err.data_ptr(),
-                                              _lib.stream_handle(d))
-        _lib.check(rc, "so_decode_chroma_frames")
+        args = (n, self._coding_number(coding), types, arr(packed), arr(offs), self.h, self.w, self.bs, arr(split),
+                arr(mv), int(qp), qr, qm, int(qp_offset), arr(refs0_u) if refs0_u else None,
+                arr(refs0_v) if refs0_v else None, len(refs0_u), int(nref_max), arr(out_u), arr(out_v), err.data_ptr())
+        if self.fme:
+            rc = self.lib.so_decode_chroma_frames_ex(*args, 2, _lib.stream_handle(d))
+            _lib.check(rc, "so_decode_chroma_frames_ex")
+        else:
+            rc = self.lib.so_decode_chroma_frames(*args, _lib.stream_handle(d))
+            _lib.check(rc, "so_decode_chroma_frames")
         return out_u, out_v, err
 
     # ---- metrics ---------------------------------------------------------------------------

@@ -102,7 +102,8 @@ class HostStreamDecoder:
         if output_size is not None:
             from . import scale as _scale
             # chroma is resampled when this geometry can carry it; refusals before a buffer is allocated
-            chroma = (int(dec.block_size) == 16 and not dec.FMEEnable and dec.h_pixels % 2 == 0 and dec.w_pixels % 2 == 0)
+            chroma = (int(dec.block_size) == 16 and (not dec.FMEEnable or getattr(dec, "chroma_subpel", False))
+                      and dec.h_pixels % 2 == 0 and dec.w_pixels % 2 == 0)
             plan = ((int(dec.h_pixels), int(dec.w_pixels)), _scale.check_size(output_size, "output_size", chroma),
                     _scale.check_filter(scale))
             _scale.ScalePlan.check(*plan, chroma=chroma)
@@ -114,7 +115,8 @@ class HostStreamDecoder:
         if not 1 <= self.nref <= _lib.MAX_REF:
             raise ValueError(f"nRefFrames {self.nref} outside [1, {_lib.MAX_REF}]")
         self.fme = bool(dec.FMEEnable)
-        self.chroma_ok = eng.bs == 16 and not self.fme
+        self.subpel = self.fme and bool(getattr(dec, "chroma_subpel", False))   # chroma from half-sample vectors
+        self.chroma_ok = eng.bs == 16 and (not self.fme or self.subpel)
         if output == "rgb" and not self.chroma_ok:
             raise NotImplementedError("output=\"rgb\" needs chroma, which needs block_size 16 and no FMEEnable")
         nb, nby, c = eng.nb, eng.nby, self.chunk
@@ -261,7 +263,10 @@ class HostStreamDecoder:
                                                self.d_qtc.data_ptr(), outs[j].data_ptr(), sh)
                     _lib.check(rc, "so_inter_recon_ex")
                     state["refs"] = (refs + [outs[j]])[-self.nref:]
-                    if chroma:                             # while the dense set holds this frame's motion
+                    if chroma and self.fused:              # while the dense set holds this frame's motion
+                        self._fused_chroma(s, j, [1], cpacked[j:j + 1], coffs[j:j + 1], [self.d_split], [self.d_mv],
+                                           rows[j:j + 1], maps[j:j + 1], ps[j:j + 1], hdr, state, coding)
+                    elif chroma:
                         self._dense_chroma(s, j, 1, cpacked[j], coffs[j], rows[j], maps[j], ps[j], hdr, state, bits, sh)
             else:
                 # While the list is short (after an I-frame, nRefFrames > 1) a stream of this
@@ -287,16 +292,13 @@ class HostStreamDecoder:
             if chroma and not self.fused:
                 if types[0] == 0:
                     self._dense_chroma(s, 0, 0, cpacked[0], coffs[0], rows[0], maps[0], ps[0], hdr, state, bits, sh)
-            elif chroma:
-                if types[0] == 0:
-                    state["refs_u"], state["refs_v"] = [], []
-                cu, cv = [self.cplanes[p, 0] for p in ps], [self.cplanes[p, 1] for p in ps]
-                eng.decode_chroma_frames(types, cpacked, coffs, [None] * n if types[0] == 0 else list(self.split[:n]),
-                                         [None] * n if types[0] == 0 else list(self.mv[:n]), state["refs_u"],
-                                         state["refs_v"], self.nref, int(self.dec.Qp), int(hdr["chroma_qp_offset"]),
-                                         rows, maps, coding=coding, out_u=cu, out_v=cv, err=s.err[1])
-                state["refs_u"] = (state["refs_u"] + cu)[-self.nref:]
-                state["refs_v"] = (state["refs_v"] + cv)[-self.nref:]
+            elif chroma and types[0] == 0:
+                state["refs_u"], state["refs_v"] = [], []
+                self._fused_chroma(s, 0, types, cpacked, coffs, [None] * n, [None] * n, rows, maps, ps, hdr, state,
+                                   coding)
+            elif chroma and not self.fme:                  # under FME every frame went with its luma above
+                self._fused_chroma(s, 0, types, cpacked, coffs, list(self.split[:n]), list(self.mv[:n]), rows, maps,
+                                   ps, hdr, state, coding)
             if self.out_hw:
                 eng.scale_yuv420(outs, [self.cplanes[p] for p in ps] if chroma else None, self.scale_plan,
                                  src_hw=self.scale_plan.src_hw, out_y=s.sy_d[:n],
@@ -328,6 +330,16 @@ class HostStreamDecoder:
         for p in ps:
             self.plane_ev[p] = s.down
 
+    def _fused_chroma(self, s, j0, types, cpacked, coffs, split, mv, rows, maps, ps, hdr, state, coding) -> None:
+        """Frames j0.. of the unit through so_decode_chroma_frames (_ex under FME: Engine picks it),
+        their error words from s.err[1, j0]."""
+        cu, cv = [self.cplanes[p, 0] for p in ps], [self.cplanes[p, 1] for p in ps]
+        self.eng.decode_chroma_frames(types, cpacked, coffs, split, mv, state["refs_u"], state["refs_v"], self.nref,
+                                      int(self.dec.Qp), int(hdr["chroma_qp_offset"]), rows, maps, coding=coding,
+                                      out_u=cu, out_v=cv, err=s.err[1, j0:])
+        state["refs_u"] = (state["refs_u"] + cu)[-self.nref:]
+        state["refs_v"] = (state["refs_v"] + cv)[-self.nref:]
+
     def _dense_chroma(self, s, j, ft, cpacked, coffs, rows, maps, p, hdr, state, bits, sh) -> None:
         """Frame j of the unit through so_unpack_chroma_frames(_bits) + so_chroma_recon_frame, the
         luma motion taken from the dense set (fused=False)."""
@@ -339,13 +351,14 @@ class HostStreamDecoder:
         if ft == 0:
             state["refs_u"], state["refs_v"] = [], []
         ru, rv = state["refs_u"], state["refs_v"]
-        rc = lib.so_chroma_recon_frame(_lib.ref_array(ru) if ft else None, _lib.ref_array(rv) if ft else None, len(ru),
-                                       eng.h, eng.w, eng.bs, ft, self.d_split.data_ptr() if ft else None,
-                                       self.d_mv.data_ptr() if ft else None, int(self.dec.Qp), _lib.ptr(rows),
-                                       _lib.ptr(maps), int(hdr["chroma_qp_offset"]), self.d_qc[0].data_ptr(),
-                                       self.d_qc[1].data_ptr(), self.cplanes[p, 0].data_ptr(),
-                                       self.cplanes[p, 1].data_ptr(), sh)
-        _lib.check(rc, "so_chroma_recon_frame")
+        args = (_lib.ref_array(ru) if ft else None, _lib.ref_array(rv) if ft else None, len(ru), eng.h, eng.w, eng.bs,
+                ft, self.d_split.data_ptr() if ft else None, self.d_mv.data_ptr() if ft else None, int(self.dec.Qp),
+                _lib.ptr(rows), _lib.ptr(maps), int(hdr["chroma_qp_offset"]), self.d_qc[0].data_ptr(),
+                self.d_qc[1].data_ptr(), self.cplanes[p, 0].data_ptr(), self.cplanes[p, 1].data_ptr())
+        if self.subpel:
+            _lib.check(lib.so_chroma_recon_frame_ex(*args, 2, sh), "so_chroma_recon_frame_ex")
+        else:
+            _lib.check(lib.so_chroma_recon_frame(*args, sh), "so_chroma_recon_frame")
         state["refs_u"] = (ru + [self.cplanes[p, 0]])[-self.nref:]
         state["refs_v"] = (rv + [self.cplanes[p, 1]])[-self.nref:]
 
@@ -385,7 +398,7 @@ class HostStreamDecoder:
                 raise ValueError(f"{path}: {hdr['w']}x{hdr['h']} bs {hdr['bs']} does not match this decoder")
             if self.output == "rgb" and not hdr["chroma"]:
                 raise ValueError(f"{path}: a luma-only file has no chroma to make RGB from (output=\"rgb\")")
-            if hdr["chroma"] and self.fme:
+            if hdr["chroma"] and self.fme and not self.subpel:
                 raise NotImplementedError("chroma with FMEEnable is not built")
             if hdr["chroma"] and eng.bs != 16:
                 raise NotImplementedError("chroma needs block_size 16")

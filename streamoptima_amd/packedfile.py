@@ -24,6 +24,12 @@ block_bytes (cblock_bytes) lets the GPU decoder (so_unpack_frames, so_unpack_chr
 every block (chroma record) in parallel: the offsets are their exclusive prefix sums.  The
 writer (write_frames: host data in; write packs device symbols and calls it) picks layout 0
 whenever it can, so a luma-only GOP without QP maps gives the file it always gave.
+
+The precision of the motion vectors is not in the file: like FMEEnable itself (half-sample luma
+vectors), which the reference's decoder takes as a constructor argument, it belongs to the
+decoder.  That holds for chroma under FMEEnable too: a file written by a codec with
+chroma_subpel=True has the same layout 1 as any other, and is read by a decoder built with
+FMEEnable=True and chroma_subpel=True; one built without chroma_subpel refuses it.
 """
 from __future__ import annotations
 

@@ -8,9 +8,12 @@
   * the 4K 30-frame I+P GOP (the benchmark's configs[2], workloads.WORKLOADS["4k"]) through
     Y_Video_codec.encode_device with chroma off and on, evented per GOP, the two alternating.
 
+--fme takes an FMEEnable codec with chroma_subpel=True instead: the luma vectors are half-sample
+and the chroma launches are the quarter-sample (mv_frac_bits 2) instantiations.
+
 Prints one JSON line; DESIGN.md "Chroma 4:2:0" quotes it.
 
-    python tools/chroma_time.py [--reps 40] [--gop-reps 12] [--warmup 5]
+    python tools/chroma_time.py [--reps 40] [--gop-reps 12] [--warmup 5] [--fme]
 """
 import argparse
 import json
@@ -51,6 +54,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--gop-reps", type=int, default=12)
+    ap.add_argument("--fme", action="store_true", help="FMEEnable codec, chroma_subpel=True (quarter-sample chroma)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("chroma_time.py needs the GPU (a CPU run measures nothing)")
@@ -59,7 +63,9 @@ def main():
     h, w, f = cfg["h"], cfg["w"], cfg["frames"]
 
     def codec(chroma):
-        return Y_Video_codec(h, w, f, 16, 16, cfg["qp"], cfg["intra_dur"], 0, 0.015, False, device=dev, chroma=chroma)
+        kw = dict(FMEEnable=True, chroma_subpel=True) if a.fme else {}
+        return Y_Video_codec(h, w, f, 16, 16, cfg["qp"], cfg["intra_dur"], 0, 0.015, False, device=dev, chroma=chroma,
+                             **kw)
     off, on = codec(False), codec(True)
     eng = on.engine()
     hp, wp = eng.h, eng.w
@@ -126,7 +132,7 @@ def main():
     bytes_frame = 2 * (npx * (1 + 1 + 1 + 2) + nb * (1 + 24 + 4 + 4))
     med = statistics.median(t_k)
     print(json.dumps({
-        "tool": "chroma_time", "height": h, "width": w, "frames": f, "reps": a.reps, "gop_reps": a.gop_reps,
+        "tool": "chroma_time", "fme": bool(a.fme), "mv_frac_bits": 2 if a.fme else 1, "height": h, "width": w, "frames": f, "reps": a.reps, "gop_reps": a.gop_reps,
         "chroma_us_per_frame": round(1e3 * med, 2), "chroma_us_per_frame_min": round(1e3 * min(t_k), 2),
         "chroma_bytes_per_frame": bytes_frame, "chroma_bytes_per_s": round(bytes_frame / (1e-3 * med), 0),
         "share_of_hbm_peak": round(bytes_frame / (1e-3 * med) / HBM_PEAK, 4),
