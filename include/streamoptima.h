@@ -955,6 +955,91 @@ int so_unpack_chroma_frames_bits(int nframes, const uint8_t* const* packed,
                                  const uint32_t* const* offs, int nb, int16_t* const* qtc_u,
                                  int16_t* const* qtc_v, int32_t* err, void* stream);
 
+/*
+ * Both streams in the "huff" coding (so_packhuff.hip; container coding 3): the symbols of the
+ * "bits" coding, in the same order, as canonical Huffman codes from tables built per frame.
+ * Records stay byte-aligned, so the offsets, the totals, the capacity guard, the _after placement
+ * and the parallel decode work as above.  The model is tests/packhuffref.py; host decoders:
+ * bitstream.unpack_frame_huff / unpack_chroma_frame_huff.
+ *
+ * Bits are written MSB-first within each byte.
+ * A value v (mv value, token or coefficient alike): z = zz(v), 0 <= z <= 65535.
+ *   z < 32:   symbol z, no extra bits.
+ *   else:     n = bit_length(z) (6..16); symbol 32 + n - 6, then the low n - 1 bits of z, raw.
+ *   43 symbols.  Code lengths are 1..15 (0: the symbol is absent), so a code and its extra bits
+ *   are at most 30 bits.
+ * Contexts: cls(p) = min(bit_length(p), 6), p the scan position inside the (sub-)block: for a
+ *   token the number of coefficients covered before it, for a coefficient its own position.
+ *   Luma has 15 tables per frame, in this order: mv, tok0..tok6, coef0..coef6; chroma 14, shared by
+ *   U and V: tok0..tok6, coef0..coef6.  An mv value is coded with table mv, a token with
+ *   tok[cls(p)], a coefficient with coef[cls(p)].
+ * One luma block: split, 1 raw bit; the mv values (the values and order of the other codings);
+ *   each (sub-)block's token list ("-L" then L values, "Z", a trailing "0"); zero bits up to the
+ *   next byte boundary.  There is no k field.
+ * One chroma record: U's list, V's list (nn = 64), zero bits up to the next byte boundary.
+ * Tables: codes are canonical -- ordered by (length, symbol), the first code of a length being
+ *   (the previous length's first code + its number of codes) << 1, starting from 0 at length 1.
+ *   A table is transmitted as its 43 lengths, 4 bits each, high nibble first; the frame's tables
+ *   follow each other in the order above: 645 nibbles in 323 bytes for luma, 602 in 301 for chroma,
+ *   the last nibble of the luma bytes 0.  They are the first bytes of record 0 of the frame:
+ *   record 0 is the table bytes, then its codes; offs and the per-record lengths count them in.
+ *   A decoder reads them from packed + offs[0] before any record.
+ * Canonical lengths (what so_pack_frames_huff / so_pack_chroma_frames_huff write): Huffman's
+ *   algorithm on the frame's symbol counts per table.  The nodes are numbered: the leaf of symbol
+ *   s is node s, merged nodes are 43, 44, ... in the order they are made.  Each step removes the two
+ *   smallest nodes by (weight, node number) and makes a node of their summed weight; only symbols
+ *   with a non-zero count take part.  A symbol's length is its leaf's depth.  A table with one
+ *   used symbol gives it length 1; unused symbols get 0.  If the longest code exceeds 15, every
+ *   non-zero count c is replaced by (c + 1) >> 1 and the table is rebuilt, until it fits.
+ * A decoder depends on the transmitted lengths only and accepts any table whose Kraft sum
+ *   (the sum of 2^-length over the non-zero lengths) is <= 1.
+ * Malformed to a decoder (so_unpack_frames_huff, so_unpack_chroma_frames_huff and the host
+ *   decoders), besides the rules of the "bits" coding that still apply (a code running past the
+ *   record's last byte; split = 1 at block size 8; the token rules; after the last list 8 or more
+ *   bits left or a set bit among them; offs[b+1] < offs[b]):
+ *   * a table whose Kraft sum exceeds 1, or a non-zero last nibble (luma), reported as record 0;
+ *   * record 0 shorter than the table bytes, reported as record 0;
+ *   * a bit pattern that matches no code of the table in force.
+ *   When the tables are malformed no record of the frame is decoded.
+ * Accepted though never written: lengths that are not the canonical ones; a 0 value inside a -L
+ *   list; a zero run reaching exactly nn written as Z.
+ *
+ * so_pack_huff_bound(nb, bs) = nb * ceil((1 + 12*30 + 30*nn + 24*(nn/2 + 4)) / 8) + 323, nn = bs^2:
+ *   the argument of so_pack_bits_bound value by value -- 12 mv values and nn coefficients of at
+ *   most 30 bits, nn/2 + 4 tokens (|token| <= 256: a code and 9 extra bits) -- plus the table
+ *   bytes.  0 for nb <= 0 or bs other than 8 or 16.  Record 0 at bs 16 is at most 1,725 bytes, so
+ *   every length fits a container's u16.
+ * so_pack_chroma_huff_bound(nb) = nb * ceil(2 * (30*64 + 22*36) / 8) + 301 = nb * 678 + 301.
+ * so_pack_frames_huff, so_unpack_frames_huff, so_pack_chroma_frames_huff, _huff_after,
+ *   so_unpack_chroma_frames_huff: arguments, behaviour and refusals of their _bits twins.  The
+ *   packers take the frames' counters and tables from the device's stream-ordered memory pool
+ *   and return them there: stream-ordered like everything else, no host synchronisation.  A
+ *   frame's symbol counts must stay below 2^32 in total.
+ * so_decode_p_frames / so_decode_chroma_frames do not take coding 3: a "huff" stream is decoded
+ *   with the unpack entry points followed by the reconstruction entry points.
+ */
+size_t so_pack_huff_bound(int nb, int block_size);
+int so_pack_frames_huff(int nframes, const int32_t* frame_types, const uint8_t* const* split,
+                        const int16_t* const* mv, const int16_t* const* qtc, int nb, int block_size,
+                        uint32_t* const* offs, uint8_t* const* out, unsigned long long cap,
+                        uint32_t* totals, void* stream);
+int so_unpack_frames_huff(int nframes, const int32_t* frame_types, const uint8_t* const* packed,
+                          const uint32_t* const* offs, int nb, int block_size,
+                          uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc,
+                          int32_t* err, void* stream);
+size_t so_pack_chroma_huff_bound(int nb);
+int so_pack_chroma_frames_huff(int nframes, const int16_t* const* qtc_u,
+                               const int16_t* const* qtc_v, int nb, uint32_t* const* offs,
+                               uint8_t* const* out, unsigned long long cap, uint32_t* totals,
+                               void* stream);
+int so_pack_chroma_frames_huff_after(int nframes, const int16_t* const* qtc_u,
+                                     const int16_t* const* qtc_v, int nb, uint32_t* const* offs,
+                                     uint8_t* const* out, const uint32_t* const* base,
+                                     unsigned long long cap, uint32_t* totals, void* stream);
+int so_unpack_chroma_frames_huff(int nframes, const uint8_t* const* packed,
+                                 const uint32_t* const* offs, int nb, int16_t* const* qtc_u,
+                                 int16_t* const* qtc_v, int32_t* err, void* stream);
+
 /* ---- fused decode: packed records straight to pixels (so_decode.hip) -------------------------
  * The receiving side's hot path.  Both entry points compute exactly what the unpack entry points
  * followed by the reconstruction entry points compute, without the dense int16 coefficients in

@@ -790,7 +790,8 @@ class Y_Video_codec(BlockAPI):
         """The encoded GOP as one binary file of packed symbols (packedfile.py: split / MVs /
         RLE token lists packed on the GPU, far smaller than the int16 QTC and the text lines).
         coding "varint": so_pack_frames, every number a varint; "bits": so_pack_frames_bits,
-        Exp-Golomb codes, about half the bytes.  decoder.decode_packed_file reads either.
+        Exp-Golomb codes, about half the bytes; "huff": so_pack_frames_huff, Huffman codes from
+        tables built per frame on the device, smaller again.  decoder.decode_packed_file reads all.
         The per-block QP maps of ROI / two-pass rate control travel with their frames (container
         layout 1).  Luma only: a chroma codec writes its GOP with transmit_packed420.
         Returns the file size in bytes."""
@@ -801,7 +802,7 @@ class Y_Video_codec(BlockAPI):
 
     def transmit_packed420(self, path: str, coding: str = "varint") -> int:
         """transmit_packed for a chroma=True codec: luma, the chroma coefficients
-        (so_pack_chroma_frames, or so_pack_chroma_frames_bits with coding "bits") and the QP maps,
+        (so_pack_chroma_frames, or its _bits / _huff twin with coding "bits" / "huff") and the QP maps,
         if any, in one file (packedfile.py layout 1).  decoder.decode_packed_file rebuilds Y, U
         and V from it.  Returns the file size in bytes."""
         if not self.chroma:

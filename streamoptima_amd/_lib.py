@@ -106,6 +106,13 @@ _SIGS = {
     "so_pack_chroma_frames_bits_after": ([_i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
     "so_unpack_chroma_frames": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "so_unpack_chroma_frames_bits": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
+    "so_pack_huff_bound": ([_i, _i], _sz),
+    "so_pack_frames_huff": ([_i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
+    "so_unpack_frames_huff": ([_i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
+    "so_pack_chroma_huff_bound": ([_i], _sz),
+    "so_pack_chroma_frames_huff": ([_i, _vp, _vp, _i, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
+    "so_pack_chroma_frames_huff_after": ([_i, _vp, _vp, _i, _vp, _vp, _vp, ctypes.c_ulonglong, _vp, _vp], _i),
+    "so_unpack_chroma_frames_huff": ([_i, _vp, _vp, _i, _vp, _vp, _vp, _vp], _i),
     "so_decode_p_frames": ([_i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp], _i),
     "so_decode_chroma_frames": ([_i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i,
                                  _vp, _vp, _vp, _vp], _i),

@@ -446,6 +446,124 @@ def unpack_chroma_frame_bits(buf, nb: int) -> dict:
     return out
 
 
+# ---- the "huff" coding of both streams (so_pack_frames_huff / so_pack_chroma_frames_huff) ---------
+_HUFF_SYMS, _HUFF_MAXLEN = 43, 15
+
+
+def _huff_cls(p: int) -> int:
+    return min(p.bit_length(), 6)
+
+
+class _HuffReader(_BitReader):
+    """The bit reader with values read through a frame's Huffman tables, which sit at its head:
+    ntab tables of 43 four-bit code lengths (include/streamoptima.h)."""
+
+    def __init__(self, buf, stream: str, ntab: int):
+        super().__init__(buf, stream)
+        nnib = ntab * _HUFF_SYMS
+        nbytes = (nnib + 1) // 2
+        if len(self.data) < nbytes:
+            raise ValueError(f"the {stream} is shorter than its tables")
+        nib = [x for c in self.data[:nbytes] for x in (c >> 4, c & 15)]
+        if any(nib[nnib:]):
+            raise ValueError(f"a set spare nibble after the tables of the {stream}")
+        self.pos = 8 * nbytes
+        self.tables = []
+        for t in range(ntab):
+            lens = nib[t * _HUFF_SYMS:(t + 1) * _HUFF_SYMS]
+            if sum(1 << (_HUFF_MAXLEN - n) for n in lens if n) > 1 << _HUFF_MAXLEN:
+                raise ValueError(f"table {t} of the {stream}: Kraft sum above 1")
+            rows, code = [], 0                   # per length: (first code, its symbols by symbol)
+            for n in range(1, _HUFF_MAXLEN + 1):
+                syms = [s for s in range(_HUFF_SYMS) if lens[s] == n]
+                rows.append((code, syms))
+                code = (code + len(syms)) << 1
+            self.tables.append(rows)
+
+    def value(self, t: int) -> int:
+        top = self.peek(_HUFF_MAXLEN)
+        for n, (first, syms) in enumerate(self.tables[t], 1):
+            c = (top >> (_HUFF_MAXLEN - n)) - first
+            if 0 <= c < len(syms):
+                self.take(n)
+                s = syms[c]
+                z = s if s < 32 else 1 << (s - 27) | self.take(s - 27)
+                return (z >> 1) ^ -(z & 1)
+        raise ValueError(f"a bit pattern that matches no code of table {t} in the {self.stream}")
+
+    def token_list(self, order, nn: int, tok0: int, what: str) -> np.ndarray:
+        """_token_list with the tables picked by position; tok0: the first token table."""
+        k = 0
+
+        def token() -> int:
+            return self.value(tok0 + _huff_cls(k))
+
+        def coefs(n: int) -> list:
+            return [self.value(tok0 + 7 + _huff_cls(k + i)) for i in range(n)]
+
+        q = np.zeros(nn, dtype=np.int16)
+        while k < nn:
+            t = token()
+            if t < 0:
+                if -t > nn - k:
+                    raise ValueError(f"{what}: a list of {-t} values at position {k} of {nn}")
+                q[order[k:k - t]] = coefs(-t)
+                k -= t
+            elif t == 0:
+                break
+            else:
+                if t > nn - k:
+                    raise ValueError(f"{what}: a run of {t} zeros at position {k} of {nn}")
+                k += t
+        return q
+
+
+def unpack_frame_huff(buf, nb: int, bs: int, frame_type: int) -> dict:
+    """One frame's packed stream in the "huff" coding (so_pack_frames_huff; the format is in
+    include/streamoptima.h) -> {"split", "mv", "qtc"} as unpack_frame.  Reads the 15 tables at the
+    frame's head, then parses sequentially, skipping to the next byte boundary after each block,
+    so it needs no offsets.  Raises ValueError on malformed input, by the rules of
+    so_unpack_frames_huff: bytes shorter than the tables, a table with a Kraft sum above 1, a set
+    spare nibble, a bit pattern that matches no code, a code running past the last byte, split = 1
+    at block size 8, the token rules of unpack_frame, a set pad bit, bytes after the last block."""
+    r = _HuffReader(buf, "packed stream", 15)
+    inter = frame_type == 1
+    split = np.zeros(nb, dtype=np.uint8)
+    mv = np.zeros((nb, 4, 3) if inter else (nb, 4), dtype=np.int16)
+    qtc = np.zeros((nb, bs * bs), dtype=np.int16)
+    sb = bs // 2
+    for b in range(nb):
+        sp = r.take(1)
+        if sp and bs != 16:
+            raise ValueError(f"block {b}: split at block size {bs}")
+        split[b] = sp
+        nmv = (4 if sp else 1) * (3 if inter else 1)
+        mv[b].reshape(-1)[:nmv] = [r.value(0) for _ in range(nmv)]
+        for n, off in ([(sb, j * sb * sb) for j in range(4)] if sp else [(bs, 0)]):
+            qtc[b, off:off + n * n] = r.token_list(scan_order(n), n * n, 1, f"block {b}")
+        if r.pad():
+            raise ValueError(f"block {b}: a set bit in the padding")
+    if r.left():
+        raise ValueError(f"{r.left()} bytes after the last block")
+    return {"split": split, "mv": mv, "qtc": qtc}
+
+
+def unpack_chroma_frame_huff(buf, nb: int) -> dict:
+    """One frame's packed chroma stream in the "huff" coding (so_pack_chroma_frames_huff) ->
+    {"qtc_u", "qtc_v"} as unpack_chroma_frame: the 14 tables at the frame's head, then the records
+    in sequence.  Raises ValueError by the rules of so_unpack_chroma_frames_huff."""
+    r = _HuffReader(buf, "packed chroma stream", 14)
+    q = np.zeros((2, nb, 64), dtype=np.int16)
+    for b in range(nb):
+        for j in range(2):
+            q[j, b] = r.token_list(scan_order(8), 64, 0, f"record {b}")
+        if r.pad():
+            raise ValueError(f"record {b}: a set bit in the padding")
+    if r.left():
+        raise ValueError(f"{r.left()} bytes after the last record")
+    return {"qtc_u": q[0], "qtc_v": q[1]}
+
+
 # ---- chroma residual line (build extension: chroma 4:2:0) ------------------------------------------
 def chroma_residual_line(u_blocks, v_blocks) -> str:
     """One frame's chroma coefficients: U's entropy_encoder_frame line at block size 8, '|', V's

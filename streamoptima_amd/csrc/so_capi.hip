@@ -1404,8 +1404,9 @@ static int check_pack_counts(const char* fn, int bs, int nb, int nframes) {
     return SO_OK;
 }
 
-// validation and launch of both codings of the stream (bits: so_packbits.hip)
-static int pack_frames_any(const char* fn, bool bits, int nframes, const int32_t* frame_types,
+// validation and launch of every coding of the stream (bits: so_packbits.hip, huff: so_packhuff.hip)
+enum PackCoding { kVarint = 0, kBits = 1, kHuff = 2 };
+static int pack_frames_any(const char* fn, int bits, int nframes, const int32_t* frame_types,
                            const uint8_t* const* split, const int16_t* const* mv, const int16_t* const* qtc, int nb,
                            int bs, uint32_t* const* offs, uint8_t* const* out, unsigned long long cap,
                            uint32_t* totals, void* stream) {
@@ -1421,11 +1422,12 @@ static int pack_frames_any(const char* fn, bool bits, int nframes, const int32_t
         }
         fr[i] = PackFrame{split[i], mv[i], qtc[i], offs[i], out[i], frame_types[i]};
     }
+    if (bits == kHuff) return pack_huff_frames_launch(fr.data(), nframes, nb, bs, cap, totals, (hipStream_t)stream);
     return bits ? pack_bits_frames_launch(fr.data(), nframes, nb, bs, cap, totals, (hipStream_t)stream)
                 : pack_frames_launch(fr.data(), nframes, nb, bs, cap, totals, (hipStream_t)stream);
 }
 
-static int unpack_frames_any(const char* fn, bool bits, int nframes, const int32_t* frame_types,
+static int unpack_frames_any(const char* fn, int bits, int nframes, const int32_t* frame_types,
                              const uint8_t* const* packed, const uint32_t* const* offs, int nb, int bs,
                              uint8_t* const* split, int16_t* const* mv, int16_t* const* qtc, int32_t* err,
                              void* stream) {
@@ -1442,6 +1444,7 @@ static int unpack_frames_any(const char* fn, bool bits, int nframes, const int32
         }
         fr[i] = UnpackFrame{packed[i], offs[i], split[i], mv[i], qtc[i], frame_types[i]};
     }
+    if (bits == kHuff) return unpack_huff_frames_launch(fr.data(), nframes, nb, bs, err, (hipStream_t)stream);
     return bits ? unpack_bits_frames_launch(fr.data(), nframes, nb, bs, err, (hipStream_t)stream)
                 : unpack_frames_launch(fr.data(), nframes, nb, bs, err, (hipStream_t)stream);
 }
@@ -1480,11 +1483,35 @@ int so_unpack_frames_bits(int nframes, const int32_t* frame_types, const uint8_t
                              err, stream);
 }
 
-// ---- the chroma coefficients as a packed stream, both codings (so_packchroma.hip) ------------
+// ---- the same stream in the "huff" coding (so_packhuff.hip) ---------------------------------
+size_t so_pack_huff_bound(int nb, int bs) {
+    if (nb <= 0 || (bs != 16 && bs != 8)) return 0;
+    return (size_t)nb * pack_huff_block_bound(bs) + kHuffLumaTableBytes;
+}
+
+int so_pack_frames_huff(int nframes, const int32_t* frame_types, const uint8_t* const* split,
+                        const int16_t* const* mv, const int16_t* const* qtc, int nb, int bs, uint32_t* const* offs,
+                        uint8_t* const* out, unsigned long long cap, uint32_t* totals, void* stream) {
+    return pack_frames_any("so_pack_frames_huff", kHuff, nframes, frame_types, split, mv, qtc, nb, bs, offs, out, cap,
+                           totals, stream);
+}
+
+int so_unpack_frames_huff(int nframes, const int32_t* frame_types, const uint8_t* const* packed,
+                          const uint32_t* const* offs, int nb, int bs, uint8_t* const* split, int16_t* const* mv,
+                          int16_t* const* qtc, int32_t* err, void* stream) {
+    return unpack_frames_any("so_unpack_frames_huff", kHuff, nframes, frame_types, packed, offs, nb, bs, split, mv, qtc,
+                             err, stream);
+}
+
+// ---- the chroma coefficients as a packed stream, every coding (so_packchroma.hip, so_packhuff.hip)
 size_t so_pack_chroma_bound(int nb) { return nb <= 0 ? 0 : (size_t)nb * pack_chroma_record_bound(false); }
 size_t so_pack_chroma_bits_bound(int nb) { return nb <= 0 ? 0 : (size_t)nb * pack_chroma_record_bound(true); }
 
-static int pack_chroma_any(const char* fn, bool bits, int nframes, const int16_t* const* qtc_u,
+size_t so_pack_chroma_huff_bound(int nb) {
+    return nb <= 0 ? 0 : (size_t)nb * kChromaHuffBound + kHuffChromaTableBytes;
+}
+
+static int pack_chroma_any(const char* fn, int bits, int nframes, const int16_t* const* qtc_u,
                            const int16_t* const* qtc_v, int nb, uint32_t* const* offs, uint8_t* const* out,
                            bool after, const uint32_t* const* base, unsigned long long cap, uint32_t* totals,
                            void* stream) {
@@ -1498,10 +1525,12 @@ static int pack_chroma_any(const char* fn, bool bits, int nframes, const int16_t
         if (after) SO_NEED(base[i], fn);
         fr[i] = ChromaPackFrame{qtc_u[i], qtc_v[i], offs[i], out[i], after ? base[i] : nullptr};
     }
+    if (bits == kHuff)
+        return pack_chroma_huff_frames_launch(fr.data(), nframes, nb, after, cap, totals, (hipStream_t)stream);
     return pack_chroma_frames_launch(fr.data(), nframes, nb, bits, after, cap, totals, (hipStream_t)stream);
 }
 
-static int unpack_chroma_any(const char* fn, bool bits, int nframes, const uint8_t* const* packed,
+static int unpack_chroma_any(const char* fn, int bits, int nframes, const uint8_t* const* packed,
                              const uint32_t* const* offs, int nb, int16_t* const* qtc_u, int16_t* const* qtc_v,
                              int32_t* err, void* stream) {
     SO_TRY(check_pack_counts(fn, 16, nb, nframes));
@@ -1512,6 +1541,7 @@ static int unpack_chroma_any(const char* fn, bool bits, int nframes, const uint8
         SO_NEED(packed[i], fn); SO_NEED(offs[i], fn); SO_NEED(qtc_u[i], fn); SO_NEED(qtc_v[i], fn);
         fr[i] = ChromaUnpackFrame{packed[i], offs[i], qtc_u[i], qtc_v[i]};
     }
+    if (bits == kHuff) return unpack_chroma_huff_frames_launch(fr.data(), nframes, nb, err, (hipStream_t)stream);
     return unpack_chroma_frames_launch(fr.data(), nframes, nb, bits, err, (hipStream_t)stream);
 }
 
@@ -1551,6 +1581,26 @@ int so_unpack_chroma_frames(int nframes, const uint8_t* const* packed, const uin
 int so_unpack_chroma_frames_bits(int nframes, const uint8_t* const* packed, const uint32_t* const* offs, int nb,
                                  int16_t* const* qtc_u, int16_t* const* qtc_v, int32_t* err, void* stream) {
     return unpack_chroma_any("so_unpack_chroma_frames_bits", true, nframes, packed, offs, nb, qtc_u, qtc_v, err,
+                             stream);
+}
+
+int so_pack_chroma_frames_huff(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
+                               uint32_t* const* offs, uint8_t* const* out, unsigned long long cap, uint32_t* totals,
+                               void* stream) {
+    return pack_chroma_any("so_pack_chroma_frames_huff", kHuff, nframes, qtc_u, qtc_v, nb, offs, out, false, nullptr,
+                           cap, totals, stream);
+}
+
+int so_pack_chroma_frames_huff_after(int nframes, const int16_t* const* qtc_u, const int16_t* const* qtc_v, int nb,
+                                     uint32_t* const* offs, uint8_t* const* out, const uint32_t* const* base,
+                                     unsigned long long cap, uint32_t* totals, void* stream) {
+    return pack_chroma_any("so_pack_chroma_frames_huff_after", kHuff, nframes, qtc_u, qtc_v, nb, offs, out, true, base,
+                           cap, totals, stream);
+}
+
+int so_unpack_chroma_frames_huff(int nframes, const uint8_t* const* packed, const uint32_t* const* offs, int nb,
+                                 int16_t* const* qtc_u, int16_t* const* qtc_v, int32_t* err, void* stream) {
+    return unpack_chroma_any("so_unpack_chroma_frames_huff", kHuff, nframes, packed, offs, nb, qtc_u, qtc_v, err,
                              stream);
 }
 

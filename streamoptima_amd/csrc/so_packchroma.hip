@@ -22,41 +22,6 @@
 
 namespace so {
 
-// A record's inputs, loaded one record ahead: lanes 0..31 hold U's 64 coefficients (two each,
-// row-major), lanes 32..63 V's.
-struct ChromaIn {
-    uint32_t q;
-    uint32_t o0, o1;  // offs[b], offs[b + 1] (write pass)
-};
-
-// The write pass's view of a frame: `out` already moved to the frame's base, `cap` lowered by it
-// (0 when the base alone passes it: no record of one byte or more fits).
-struct ChromaDst {
-    uint8_t* out;
-    unsigned long long cap;
-};
-
-template <bool WRITE>
-SO_DEV ChromaIn chroma_load(const ChromaPackFrame& f, int b, int nb, int lane) {
-    b = b < nb ? b : nb - 1;   // branch-free: every lane loads, the index clamped
-    const int16_t* src = lane < 32 ? f.qu : f.qv;
-    ChromaIn in;
-    in.q = *reinterpret_cast<const u32_alias*>(src + (size_t)b * 64 + (lane & 31) * 2);
-    in.o0 = WRITE ? f.offs[b] : 0;
-    in.o1 = WRITE ? f.offs[b + 1] : 0;
-    return in;
-}
-
-// What both codings share: the record through LDS into scan order, lane l owning positions 2l
-// and 2l + 1 of the U|V sequence, and the runs of its two lists (so_packfmt.h pack_runs at R = 2,
-// S = 64).
-SO_DEV PackRuns<2> chroma_runs(const ChromaIn& in, int lane, int16_t* __restrict__ sq, const int* idx) {
-    reinterpret_cast<u32_alias*>(sq)[lane] = in.q;
-    __builtin_amdgcn_wave_barrier();   // LDS ops of one wave run in order
-    const int v[2] = {sq[idx[0]], sq[idx[1]]};
-    return pack_runs<2>(v, 64, lane);
-}
-
 // ---- varint coding -------------------------------------------------------------------------------
 template <bool WRITE>
 SO_DEV void pack_chroma_one(const ChromaPackFrame& f, int b, const ChromaDst& d, int lane, const ChromaIn& in,

@@ -1,6 +1,6 @@
-// so_packfmt.h — the packed stream's format, stated once for its three device sources (so_pack.hip:
-// luma, varints; so_packbits.hip: luma, Exp-Golomb bits; so_packchroma.hip: chroma, both codings)
-// and for so_capi.hip.  The format itself is described at the top of those sources and is normative
+// so_packfmt.h — the packed stream's format, stated once for its four device sources (so_pack.hip:
+// luma, varints; so_packbits.hip: luma, Exp-Golomb bits; so_packchroma.hip: chroma, both codings;
+// so_packhuff.hip: luma and chroma, per-frame Huffman tables) and for so_capi.hip.  The format itself is described at the top of those sources and is normative
 // in include/streamoptima.h; this header holds what they share.
 //
 // Two layers:
@@ -82,6 +82,23 @@ constexpr int kChromaBitsBound = (2 + 2 * (33 * 64 + 19 * 36) + 7) / 8;       //
 constexpr size_t pack_chroma_record_bound(bool bits) { return bits ? kChromaBitsBound : kChromaBound; }
 constexpr int kChromaStageWords = (kChromaBitsBound + 3) / 4 + 1;
 
+// Huffman coding ("huff"): 43 symbols per table, code lengths 1..15 in 4 bits each; luma has 15 tables
+// (mv, tok0..6, coef0..6), chroma 14 (tok0..6, coef0..6), at the head of record 0.  A value is a code
+// of at most 15 bits and at most 15 raw bits; a token (|token| <= 256, chroma 64) at most 15 + 9 (7).
+constexpr int kHuffSyms = 43, kHuffMaxLen = 15, kHuffCtx = 7;
+constexpr int kHuffLumaTables = 1 + 2 * kHuffCtx, kHuffChromaTables = 2 * kHuffCtx;
+constexpr int huff_table_bytes(int ntab) { return (ntab * kHuffSyms + 1) / 2; }
+constexpr int kHuffLumaTableBytes = huff_table_bytes(kHuffLumaTables);       // 323
+constexpr int kHuffChromaTableBytes = huff_table_bytes(kHuffChromaTables);   // 301
+constexpr int pack_huff_block_bits(int bs) { return 1 + 12 * 30 + 30 * bs * bs + 24 * (bs * bs / 2 + 4); }
+constexpr size_t pack_huff_block_bound(int bs) { return (size_t)(pack_huff_block_bits(bs) + 7) / 8; }
+constexpr int kHuffStageWords = (pack_huff_block_bits(16) + 31) / 32 + 1;
+constexpr int kChromaHuffBound = (2 * (30 * 64 + 22 * 36) + 7) / 8;          // 678
+constexpr int kChromaHuffStageWords = (kChromaHuffBound + 3) / 4 + 1;
+// a frame's device scratch, in 32-bit words: the counts, the (length << 16 | code) entries, the table bytes
+constexpr int kHuffTableWords = kHuffLumaTables * kHuffSyms;
+constexpr int kHuffScratchWords = 2 * kHuffTableWords + (kHuffLumaTableBytes + 3) / 4 + 1;
+
 // so_pack.hip
 int pack_frames_launch(const PackFrame* frames, int nframes, int nb, int bs, unsigned long long cap, uint32_t* totals,
                        hipStream_t st);
@@ -97,6 +114,15 @@ int pack_chroma_frames_launch(const ChromaPackFrame* frames, int nframes, int nb
                               unsigned long long cap, uint32_t* totals, hipStream_t st);
 int unpack_chroma_frames_launch(const ChromaUnpackFrame* frames, int nframes, int nb, bool bits, int32_t* err,
                                 hipStream_t st);
+
+// so_packhuff.hip
+int pack_huff_frames_launch(const PackFrame* frames, int nframes, int nb, int bs, unsigned long long cap,
+                            uint32_t* totals, hipStream_t st);
+int unpack_huff_frames_launch(const UnpackFrame* frames, int nframes, int nb, int bs, int32_t* err, hipStream_t st);
+int pack_chroma_huff_frames_launch(const ChromaPackFrame* frames, int nframes, int nb, bool after,
+                                   unsigned long long cap, uint32_t* totals, hipStream_t st);
+int unpack_chroma_huff_frames_launch(const ChromaUnpackFrame* frames, int nframes, int nb, int32_t* err,
+                                     hipStream_t st);
 
 // ---- coding primitives --------------------------------------------------------------------------
 SO_DEV uint32_t zz(int v) { return ((uint32_t)v << 1) ^ (uint32_t)(v >> 31); }
@@ -578,6 +604,42 @@ SO_DEV PackRuns<LumaIdx<bs>::R> luma_runs(const PackIn& in, int sp, int lane, in
 #pragma unroll
     for (int j = 0; j < R; ++j) v[j] = sq[S == 64 && bs == 16 ? idx.split[j] : idx.whole[j]];
     return pack_runs<R>(v, S, lane);
+}
+
+// ---- a chroma record's inputs and runs (every coding) ------------------------------------------
+// A record's inputs, loaded one record ahead: lanes 0..31 hold U's 64 coefficients (two each,
+// row-major), lanes 32..63 V's.
+struct ChromaIn {
+    uint32_t q;
+    uint32_t o0, o1;  // offs[b], offs[b + 1] (write pass)
+};
+
+// The write pass's view of a frame: `out` already moved to the frame's base, `cap` lowered by it
+// (0 when the base alone passes it: no record of one byte or more fits).
+struct ChromaDst {
+    uint8_t* out;
+    unsigned long long cap;
+};
+
+template <bool WRITE>
+SO_DEV ChromaIn chroma_load(const ChromaPackFrame& f, int b, int nb, int lane) {
+    b = b < nb ? b : nb - 1;   // branch-free: every lane loads, the index clamped
+    const int16_t* src = lane < 32 ? f.qu : f.qv;
+    ChromaIn in;
+    in.q = *reinterpret_cast<const u32_alias*>(src + (size_t)b * 64 + (lane & 31) * 2);
+    in.o0 = WRITE ? f.offs[b] : 0;
+    in.o1 = WRITE ? f.offs[b + 1] : 0;
+    return in;
+}
+
+// What both codings share: the record through LDS into scan order, lane l owning positions 2l
+// and 2l + 1 of the U|V sequence, and the runs of its two lists (so_packfmt.h pack_runs at R = 2,
+// S = 64).
+SO_DEV PackRuns<2> chroma_runs(const ChromaIn& in, int lane, int16_t* __restrict__ sq, const int* idx) {
+    reinterpret_cast<u32_alias*>(sq)[lane] = in.q;
+    __builtin_amdgcn_wave_barrier();   // LDS ops of one wave run in order
+    const int v[2] = {sq[idx[0]], sq[idx[1]]};
+    return pack_runs<2>(v, 64, lane);
 }
 
 // ---- loops ---------------------------------------------------------------------------------------

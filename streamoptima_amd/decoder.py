@@ -273,10 +273,10 @@ class decoder:
 
     def decode_packed_file(self, path: str, save_decoded_frames=True):
         """Encoder.transmit_packed's or transmit_packed420's file (packedfile.py, both layouts): the
-        packed streams go to the GPU, so_unpack_frames (or so_unpack_frames_bits, by the file's
+        packed streams go to the GPU, so_unpack_frames (or so_unpack_frames_bits / _huff, by the file's
         coding) restores split / mv / qtc of every block in parallel, and the frames are rebuilt
         by the same kernels as decode().  Per-block QP maps in the file are applied.  With chroma
-        in the file so_unpack_chroma_frames (_bits) restores the coefficients and U and V are
+        in the file so_unpack_chroma_frames (_bits, _huff) restores the coefficients and U and V are
         rebuilt too (self.decoded_chroma, save_yuv420)."""
         from . import packedfile
         eng = self._eng()
@@ -315,7 +315,8 @@ class decoder:
                              scale: str = "lanczos3") -> dict:
         """decode_packed_file's frames without its footprint (hostdecode.HostStreamDecoder): the file
         is read as it goes, P-frames and chroma are decoded from the packed records straight to
-        pixels (so_decode_p_frames, so_decode_chroma_frames), and upload, decode and download overlap
+        pixels (so_decode_p_frames, so_decode_chroma_frames; a "huff" file through the unpack and
+        reconstruction entry points instead), and upload, decode and download overlap
         with a fixed set of buffers whatever the file's length.  out_path: write the frames as a
         planar file (Y | U | V per frame; Y alone for a luma-only file) -- save_yuv420's /
         save_decoded_frames' bytes.  consume(i, y, u, v): called per frame in order with host arrays

@@ -66,6 +66,17 @@ def pack_coding_is_bits(coding: str) -> bool:
     return coding == "bits"
 
 
+PACK_CODINGS = {"varint": 1, "bits": 2, "huff": 3}     # the coding -> its container number
+
+
+def pack_coding_suffix(coding: str) -> str:
+    """The entry points' suffix for a coding of the packed stream: "" for "varint", "_bits" for
+    "bits", "_huff" for "huff" (per-frame Huffman tables); anything else raises."""
+    if coding not in PACK_CODINGS:
+        raise ValueError(f"packed stream coding {coding!r} (\"varint\", \"bits\" or \"huff\")")
+    return "" if coding == "varint" else "_" + coding
+
+
 @dataclass
 class FrameSymbols:
     """Per-frame output of the encode path (canonical layout, include/streamoptima.h)."""
@@ -620,7 +631,7 @@ class Engine:
 
     # ---- packed symbol stream (so_pack_frames / so_pack_frames_bits) -----------------------
     def pack_bound(self, nb: int | None = None, coding: str = "varint") -> int:
-        bound = self.lib.so_pack_bits_bound if pack_coding_is_bits(coding) else self.lib.so_pack_bound
+        bound = getattr(self.lib, f"so_pack{pack_coding_suffix(coding)}_bound")
         return int(bound(int(self.nb if nb is None else nb), self.bs))
 
     def pack_symbols(self, syms: list, offs: torch.Tensor | None = None, out: torch.Tensor | None = None,
@@ -632,8 +643,9 @@ class Engine:
         totals_ptr: a device address of n uint32 (hostmem.device_ptr of a page-locked host
         array) that also receives offs[i, nb] (so_pack_frames_ex).
         coding: "varint" (so_pack_frames_ex) or "bits" (so_pack_frames_bits: Exp-Golomb codes,
-        about half the bytes; bitstream.unpack_frame_bits decodes it)."""
-        bits = pack_coding_is_bits(coding)
+        about half the bytes; bitstream.unpack_frame_bits decodes it) or "huff" (so_pack_frames_huff:
+        Huffman codes from tables built per frame on the device; bitstream.unpack_frame_huff)."""
+        name = "so_pack_frames" + (pack_coding_suffix(coding) or "_ex")
         n = len(syms)
         if n == 0:
             raise ValueError("pack_symbols: no frames")
@@ -646,19 +658,18 @@ class Engine:
         if offs.shape != (n, nb + 1) or offs.dtype != torch.int32 or out.shape[0] != n or out.dtype != torch.uint8:
             raise ValueError("pack_symbols: offs must be int32 [n, nb + 1] and out uint8 [n, cap]")
         arr, types = _lib.ptr_array, _lib.i32_array([s.frame_type for s in syms])
-        pack = self.lib.so_pack_frames_bits if bits else self.lib.so_pack_frames_ex
-        rc = pack(n, types, arr([s.split for s in syms]), arr([s.mv for s in syms]),
-                  arr([s.qtc for s in syms]), nb, self.bs, arr(list(offs)), arr(list(out)),
-                  int(cap), totals_ptr, _lib.stream_handle(self.device))
-        _lib.check(rc, "so_pack_frames_bits" if bits else "so_pack_frames")
+        rc = getattr(self.lib, name)(n, types, arr([s.split for s in syms]), arr([s.mv for s in syms]),
+                                     arr([s.qtc for s in syms]), nb, self.bs, arr(list(offs)), arr(list(out)),
+                                     int(cap), totals_ptr, _lib.stream_handle(self.device))
+        _lib.check(rc, name[:-3] if name.endswith("_ex") else name)
         return offs, out
 
     def unpack_symbols(self, frame_types: list, packed: list, offs: list, coding: str = "varint") -> list:
-        """so_unpack_frames (coding "varint") or so_unpack_frames_bits ("bits"): packed streams
+        """so_unpack_frames (coding "varint"), so_unpack_frames_bits ("bits") or _huff ("huff"): packed streams
         (device uint8) + their block offsets (device int32 [nb + 1], as pack_symbols wrote them)
         -> FrameSymbols with split / mv / qtc (no recon, tokens or metrics).  Raises ValueError
         on a malformed stream (synchronises once)."""
-        name = "so_unpack_frames_bits" if pack_coding_is_bits(coding) else "so_unpack_frames"
+        name = "so_unpack_frames" + pack_coding_suffix(coding)
         n = len(packed)
         syms = [self.new_symbols(int(t)) for t in frame_types]
         err = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -674,8 +685,7 @@ class Engine:
 
     # ---- packed chroma stream (so_pack_chroma_frames / so_pack_chroma_frames_bits) ------------
     def pack_chroma_bound(self, coding: str = "varint") -> int:
-        bound = self.lib.so_pack_chroma_bits_bound if pack_coding_is_bits(coding) else self.lib.so_pack_chroma_bound
-        return int(bound(self.nb))
+        return int(getattr(self.lib, f"so_pack_chroma{pack_coding_suffix(coding)}_bound")(self.nb))
 
     def pack_chroma_symbols(self, csyms: list, offs: torch.Tensor | None = None, out: torch.Tensor | None = None,
                             totals: torch.Tensor | None = None, coding: str = "varint",
@@ -686,13 +696,13 @@ class Engine:
         out[i, :offs[i, nb]], record b starts at offs[i, b].  The default capacity never overflows.
         totals: a device int32 [n] that also receives offs[i, nb]; totals_ptr: instead of it, a
         device address of n uint32 (hostmem.device_ptr of a page-locked host array).  coding:
-        "varint" or "bits".
+        "varint", "bits" or "huff".
         after: the int32 [n, nb + 1] offsets pack_symbols filled for the same frames, earlier on this
         stream (so_pack_chroma_frames_after).  `out` is then required and is the tensor pack_symbols
         wrote, with room for both streams: frame i's chroma records go behind its luma bytes, to
         out[i, after[i, nb] + offs[i, b]], offs staying relative, and the totals receive the
         combined length after[i, nb] + offs[i, nb]."""
-        bits = pack_coding_is_bits(coding)
+        suffix = pack_coding_suffix(coding)
         n, nb = len(csyms), self.nb
         if n == 0:
             raise ValueError("pack_chroma_symbols: no frames")
@@ -724,7 +734,7 @@ class Engine:
             raise ValueError("pack_chroma_symbols: totals or totals_ptr, not both")
         tot = _lib.ptr(totals) if totals_ptr is None else int(totals_ptr)
         arr = _lib.ptr_array
-        name = "so_pack_chroma_frames_bits" if bits else "so_pack_chroma_frames"
+        name = "so_pack_chroma_frames" + suffix
         base = ()
         if after is not None:
             name += "_after"
@@ -736,11 +746,11 @@ class Engine:
         return offs, out
 
     def unpack_chroma_symbols(self, packed: list, offs: list, coding: str = "varint") -> list:
-        """so_unpack_chroma_frames (coding "varint") or so_unpack_chroma_frames_bits ("bits"):
+        """so_unpack_chroma_frames (coding "varint"), so_unpack_chroma_frames_bits ("bits") or _huff ("huff"):
         packed chroma streams (device uint8) + their record offsets (device int32 [nb + 1]) ->
         [(qtc_u, qtc_v)], int16 [nb, 64] each.  Raises ValueError on a malformed stream
         (synchronises once)."""
-        name = "so_unpack_chroma_frames_bits" if pack_coding_is_bits(coding) else "so_unpack_chroma_frames"
+        name = "so_unpack_chroma_frames" + pack_coding_suffix(coding)
         n = len(packed)
         if n == 0 or len(offs) != n:
             raise ValueError("unpack_chroma_symbols: one offsets tensor per packed stream, at least one")
@@ -760,7 +770,8 @@ class Engine:
     # ---- fused decode (so_decode_p_frames / so_decode_chroma_frames) ---------------------------
     @staticmethod
     def _coding_number(coding: str) -> int:
-        return 2 if pack_coding_is_bits(coding) else 1
+        pack_coding_suffix(coding)
+        return PACK_CODINGS[coding]
 
     def _qp_ptrs(self, qps, n: int, what: str):
         """Per-frame QP sources as a host array of device pointers: each entry None, a device

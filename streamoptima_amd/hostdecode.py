@@ -37,7 +37,7 @@ import torch
 
 from . import _lib, packedfile
 from .colour import as_colour
-from .engine import alloc_planes, pack_coding_is_bits
+from .engine import PACK_CODINGS, alloc_planes, pack_coding_suffix
 from .hostmem import pinned_empty
 from .hwqueue import dedicated_stream
 
@@ -122,9 +122,9 @@ class HostStreamDecoder:
         nb, nby, c = eng.nb, eng.nby, self.chunk
         # a frame's staging slot: u16 lengths | u16 chroma lengths | i32 row QPs | i32 QP map | luma
         # bytes | chroma bytes (the chroma bytes start 16-aligned behind the luma bytes, so one copy
-        # of the slot's head carries the frame); capacities are the packers' bounds, either coding
-        self.cap_l = max(eng.pack_bound(coding="varint"), eng.pack_bound(coding="bits"))
-        self.cap_c = max(eng.pack_chroma_bound("varint"), eng.pack_chroma_bound("bits")) if self.chroma_ok else 0
+        # of the slot's head carries the frame); capacities are the packers' bounds, any coding
+        self.cap_l = max(eng.pack_bound(coding=c) for c in PACK_CODINGS)
+        self.cap_c = max(eng.pack_chroma_bound(c) for c in PACK_CODINGS) if self.chroma_ok else 0
         self.o_clens = _a16(2 * nb)
         self.o_qrow = self.o_clens + _a16(2 * nb)
         self.o_qmap = self.o_qrow + _a16(4 * nby)
@@ -203,7 +203,8 @@ class HostStreamDecoder:
         unit, n = s.frames, len(s.frames)
         chroma = hdr["chroma"]
         coding = hdr["coding"]
-        bits = pack_coding_is_bits(coding)
+        suffix = pack_coding_suffix(coding)
+        fused = self.fused and coding != "huff"          # the fused decoders do not take "huff": unpack + recon
         with torch.cuda.stream(self.h2d):
             for j, (_, _, nl, nc, _, _) in enumerate(unit):
                 m = self.o_pay + _a16(nl) + nc
@@ -238,7 +239,7 @@ class HostStreamDecoder:
             types = [u[1] for u in unit]
             one = ctypes.c_void_p * 1
             if types[0] == 0:                              # an I-frame is a unit of its own
-                name = "so_unpack_frames_bits" if bits else "so_unpack_frames"
+                name = "so_unpack_frames" + suffix
                 rc = getattr(lib, name)(1, (ctypes.c_int32 * 1)(0), one(packed[0].data_ptr()), one(offs[0].data_ptr()),
                                         nb, eng.bs, one(self.d_split.data_ptr()), one(self.d_mv.data_ptr()),
                                         one(self.d_qtc.data_ptr()), s.err[0].data_ptr(), sh)
@@ -248,8 +249,8 @@ class HostStreamDecoder:
                                            outs[0].data_ptr(), eng.scratch.data_ptr(), sh)
                 _lib.check(rc, "so_intra_recon_ex")
                 state["refs"] = [outs[0]]
-            elif self.fme or not self.fused:               # P-frames off the dense set, one by one
-                name = "so_unpack_frames_bits" if bits else "so_unpack_frames"
+            elif self.fme or not fused:                    # P-frames off the dense set, one by one
+                name = "so_unpack_frames" + suffix
                 for j in range(n):
                     rc = getattr(lib, name)(1, (ctypes.c_int32 * 1)(1), one(packed[j].data_ptr()),
                                             one(offs[j].data_ptr()), nb, eng.bs, one(self.d_split.data_ptr()),
@@ -263,11 +264,11 @@ class HostStreamDecoder:
                                                self.d_qtc.data_ptr(), outs[j].data_ptr(), sh)
                     _lib.check(rc, "so_inter_recon_ex")
                     state["refs"] = (refs + [outs[j]])[-self.nref:]
-                    if chroma and self.fused:              # while the dense set holds this frame's motion
+                    if chroma and fused:                   # while the dense set holds this frame's motion
                         self._fused_chroma(s, j, [1], cpacked[j:j + 1], coffs[j:j + 1], [self.d_split], [self.d_mv],
                                            rows[j:j + 1], maps[j:j + 1], ps[j:j + 1], hdr, state, coding)
                     elif chroma:
-                        self._dense_chroma(s, j, 1, cpacked[j], coffs[j], rows[j], maps[j], ps[j], hdr, state, bits, sh)
+                        self._dense_chroma(s, j, 1, cpacked[j], coffs[j], rows[j], maps[j], ps[j], hdr, state, suffix, sh)
             else:
                 # While the list is short (after an I-frame, nRefFrames > 1) a stream of this
                 # project's encoder can name a reference past it: the encoder keeps its list across
@@ -289,9 +290,9 @@ class HostStreamDecoder:
                                         out_recon=outs[j:], err=s.err[0, j:])
                     refs = (refs + outs[j:])[-self.nref:]
                 state["refs"] = refs
-            if chroma and not self.fused:
+            if chroma and not fused:
                 if types[0] == 0:
-                    self._dense_chroma(s, 0, 0, cpacked[0], coffs[0], rows[0], maps[0], ps[0], hdr, state, bits, sh)
+                    self._dense_chroma(s, 0, 0, cpacked[0], coffs[0], rows[0], maps[0], ps[0], hdr, state, suffix, sh)
             elif chroma and types[0] == 0:
                 state["refs_u"], state["refs_v"] = [], []
                 self._fused_chroma(s, 0, types, cpacked, coffs, [None] * n, [None] * n, rows, maps, ps, hdr, state,
@@ -340,11 +341,13 @@ class HostStreamDecoder:
         state["refs_u"] = (state["refs_u"] + cu)[-self.nref:]
         state["refs_v"] = (state["refs_v"] + cv)[-self.nref:]
 
-    def _dense_chroma(self, s, j, ft, cpacked, coffs, rows, maps, p, hdr, state, bits, sh) -> None:
-        """Frame j of the unit through so_unpack_chroma_frames(_bits) + so_chroma_recon_frame, the
-        luma motion taken from the dense set (fused=False)."""
+    def _dense_chroma(self, s, j, ft, cpacked, coffs, rows, maps, p, hdr, state, suffix, sh) -> None:
+        """Frame j of the unit through so_unpack_chroma_frames(_bits, _huff) + so_chroma_recon_frame,
+        the luma motion taken from the dense set (fused=False, and every "huff" file)."""
         eng, lib, one = self.eng, self.eng.lib, ctypes.c_void_p * 1
-        name = "so_unpack_chroma_frames_bits" if bits else "so_unpack_chroma_frames"
+        if self.d_qc is None:                              # a fused decoder's first "huff" file
+            self.d_qc = torch.empty((2, eng.nb, 64), dtype=torch.int16, device=self.dev)
+        name = "so_unpack_chroma_frames" + suffix
         rc = getattr(lib, name)(1, one(cpacked.data_ptr()), one(coffs.data_ptr()), eng.nb, one(self.d_qc[0].data_ptr()),
                                 one(self.d_qc[1].data_ptr()), s.err[1, j:].data_ptr(), sh)
         _lib.check(rc, name)

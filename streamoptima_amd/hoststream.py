@@ -45,7 +45,7 @@ class _Buffers:
     """One GOP in flight: device frames, packed streams and their pinned host copies."""
 
     def __init__(self, eng, nframes: int, dev, chroma: bool = False, lengths: bool = False, rgb_hw=None,
-                 src_hw=None):
+                 src_hw=None, coding: str = "varint"):
         nb, F = eng.nb, nframes
         self.frames_dev = alloc_planes(F, eng.h, eng.w, dev)
         # source_size: where a unit's planes land at source size before so_scale_yuv420 writes frames_dev / uv_dev
@@ -57,7 +57,8 @@ class _Buffers:
         # input="rgb": where a unit's pictures land before so_rgb_to_yuv420 writes frames_dev / uv_dev
         self.rgb_dev = torch.empty((F, *rgb_hw, 3), dtype=torch.uint8, device=dev) if rgb_hw else None
         self.offs = torch.empty((F, nb + 1), dtype=torch.int32, device=dev)
-        cap = eng.pack_bound() + (eng.pack_chroma_bound() if chroma else 0)   # a row: luma, then chroma
+        # a row: luma, then chroma, by the coding's bounds
+        cap = eng.pack_bound(coding=coding) + (eng.pack_chroma_bound(coding) if chroma else 0)
         self.packed = torch.empty((F, cap), dtype=torch.uint8, device=dev)
         self.packed_h = pinned_empty(tuple(self.packed.shape))
         # the small host arrays in one page-locked slab (an allocation there is 2 MB at least):
@@ -76,8 +77,8 @@ class _Buffers:
             self.uv_dev = alloc_planes(F * 2, eng.h // 2, eng.w // 2, dev).view(F, 2, eng.h // 2, eng.w // 2)
             self.coffs = torch.empty((F, nb + 1), dtype=torch.int32, device=dev)
         if lengths:
-            # per-block byte counts: diff(offs) on the compute stream (a block is at most 1201 bytes,
-            # a chroma record 600), row 0 luma, row 1 chroma, and their host copy
+            # per-block byte counts: diff(offs) on the compute stream (a block is at most 1725 bytes
+            # in any coding, a chroma record 979), row 0 luma, row 1 chroma, and their host copy
             k = 2 if chroma else 1
             self.diff32 = torch.empty((k, F, nb), dtype=torch.int32, device=dev)
             self.blen = torch.empty((k, F, nb), dtype=torch.int16, device=dev)
@@ -105,8 +106,11 @@ class _PackedViews:
 
 class HostStreamEncoder:
     def __init__(self, codec, nframes: int, chunk: int = 2, nbuf: int = 1, upload: str = "chunk",
-                 lengths: bool = False, input: str = "yuv420", source_size=None, scale: str = "lanczos3"):
-        """upload: "chunk" = one H2D copy per encode unit (the I-frame, each P-run chunk), "frame"
+                 lengths: bool = False, input: str = "yuv420", source_size=None, scale: str = "lanczos3",
+                 coding: str = "varint"):
+        """coding: the packed stream's coding, "varint", "bits" or "huff" (Engine.pack_symbols); the
+        buffers are sized by its bounds and write_packed writes its version word.
+        upload: "chunk" = one H2D copy per encode unit (the I-frame, each P-run chunk), "frame"
         = one per frame.  lengths: the results also hold each frame's per-block byte counts
         ("block_bytes", and "chroma_block_bytes" with a chroma=True codec), which write_packed needs.
         input: "yuv420" = padded Y (and UV) planes from the host; "rgb" (chroma=True codecs) = pinned
@@ -118,6 +122,9 @@ class HostStreamEncoder:
         pictures, uploaded into staging planes per buffer set and resampled behind the copy on the H2D
         stream (so_scale_yuv420 with the `scale` filter: "bilinear", "bicubic" or "lanczos3") to the
         codec's h_pixels x w_pixels, padded with 128.  None: nothing is staged and nothing resampled."""
+        from .engine import pack_coding_suffix
+        pack_coding_suffix(coding)                         # refuses an unknown coding
+        self.coding = coding
         if input not in ("yuv420", "rgb"):
             raise ValueError(f"input {input!r} (\"yuv420\" or \"rgb\")")
         if input == "rgb" and not codec.chroma:
@@ -151,7 +158,8 @@ class HostStreamEncoder:
         self.rgb_hw = (self.src_hw or (int(codec.h_pixels), int(codec.w_pixels))) if input == "rgb" else None
         if host_plan:
             self.scale_plan = _scale.ScalePlan(*host_plan, chroma=self.chroma, device=self.dev)
-        self.bufs = [_Buffers(eng, self.nframes, self.dev, self.chroma, self.lengths, self.rgb_hw, self.src_hw)
+        self.bufs = [_Buffers(eng, self.nframes, self.dev, self.chroma, self.lengths, self.rgb_hw, self.src_hw,
+                              self.coding)
                      for _ in range(max(1, int(nbuf)))]
 
     @property
@@ -286,7 +294,7 @@ class HostStreamEncoder:
             else:
                 f["payload"] = p
             frames.append(f)
-        return packedfile.write_frames(path, self.eng.h, self.eng.w, self.eng.bs, self.eng.nb, "varint", frames,
+        return packedfile.write_frames(path, self.eng.h, self.eng.w, self.eng.bs, self.eng.nb, self.coding, frames,
                                        chroma_qp_offset=self.codec.chroma_qp_offset if self.chroma else None)
 
     def encode_stream(self, gops: list, intra_dur: int, consume, trace: list | None = None,
@@ -368,11 +376,12 @@ class HostStreamEncoder:
 
             def on_output(k0, k1, syms, csyms=None, b=b):
                 # the scan stores the frames' lengths straight into tot_h (so_pack_frames_ex)
-                eng.pack_symbols(syms, b.offs[k0:k1], b.packed[k0:k1], totals_ptr=b.tot_dptr + 4 * k0)
+                eng.pack_symbols(syms, b.offs[k0:k1], b.packed[k0:k1], totals_ptr=b.tot_dptr + 4 * k0,
+                                 coding=self.coding)
                 if csyms is not None:
                     # the chroma records behind each frame's luma bytes, the combined lengths into all_h
                     eng.pack_chroma_symbols(csyms, b.coffs[k0:k1], b.packed[k0:k1], after=b.offs[k0:k1],
-                                            totals_ptr=b.all_dptr + 4 * k0)
+                                            totals_ptr=b.all_dptr + 4 * k0, coding=self.coding)
                 if self.lengths:
                     for r, o in enumerate((b.offs, b.coffs) if csyms is not None else (b.offs,)):
                         torch.sub(o[k0:k1, 1:], o[k0:k1, :-1], out=b.diff32[r, k0:k1])

@@ -2,9 +2,12 @@
 the reference's two text files (transmit_bitstream, Encoder.py:1544-1573; decode_bitstream,
 decoder.py:686-709).  Little endian.  The version word is layout << 16 | coding: coding 1 is the
 varint coding of the streams (so_pack_frames, so_pack_chroma_frames), coding 2 the "bits" coding
-(so_pack_frames_bits, so_pack_chroma_frames_bits).
+(so_pack_frames_bits, so_pack_chroma_frames_bits), coding 3 the "huff" coding (so_pack_frames_huff,
+so_pack_chroma_frames_huff), whose per-frame Huffman tables are the first bytes of block 0 (chroma
+record 0) and are counted in its length: a "huff" frame whose first block is shorter than its
+tables (323 bytes, chroma 301) is rejected like lengths that do not add up.
 
-Layout 0 (version 1 or 2): luma only, no per-block QP maps.
+Layout 0 (version 1, 2 or 3): luma only, no per-block QP maps.
 
     header   b"SOPK" | u32 version | u32 H | u32 W | u32 bs | u32 nframes | u32 nb
     frame    u8 frame_type | u16 nqp | i8 qp[nqp] (per-row QPs under rate control, else 0)
@@ -39,7 +42,8 @@ import numpy as np
 import torch
 
 MAGIC = b"SOPK"
-VERSIONS = {"varint": 1, "bits": 2}              # the stream's coding -> the version word's low half
+VERSIONS = {"varint": 1, "bits": 2, "huff": 3}   # the stream's coding -> the version word's low half
+HUFF_TABLE_BYTES = {"block": 323, "chroma record": 301}   # at the head of a "huff" frame's first block / record
 FLAG_CHROMA, FLAG_QP_MAPS = 1, 2
 
 
@@ -67,7 +71,7 @@ def write_frames(path: str, h: int, w: int, bs: int, nb: int, coding: str, frame
     for none.  chroma_qp_offset goes into the header of a file with chroma.  Layout 0 when no frame
     has chroma or a QP map, else layout 1.  This is the one statement of the format's write side."""
     if coding not in VERSIONS:
-        raise ValueError(f"packed stream coding {coding!r} (\"varint\" or \"bits\")")
+        raise ValueError(f"packed stream coding {coding!r} (\"varint\", \"bits\" or \"huff\")")
     has_c = ["chroma_payload" in f or "chroma_block_bytes" in f for f in frames]
     if any(has_c) and not all("chroma_payload" in f and "chroma_block_bytes" in f for f in frames):
         raise ValueError("chroma_block_bytes and chroma_payload: both, and for every frame or for none")
@@ -102,11 +106,11 @@ def write_frames(path: str, h: int, w: int, bs: int, nb: int, coding: str, frame
 
 def write(path: str, eng, symbols: list, qp_rows: list | None = None, coding: str = "varint",
           chroma_symbols: list | None = None) -> int:
-    """Pack `symbols` (FrameSymbols on the device) in `coding` ("varint" or "bits") and write the
+    """Pack `symbols` (FrameSymbols on the device) in `coding` ("varint", "bits" or "huff") and write the
     container (write_frames); returns its size.  chroma_symbols: the frames' ChromaSymbols, packed
     in the same coding (layout 1).  Per-block QP maps (s.extra["qp_map"]) are written too (layout 1)."""
     if coding not in VERSIONS:
-        raise ValueError(f"packed stream coding {coding!r} (\"varint\" or \"bits\")")
+        raise ValueError(f"packed stream coding {coding!r} (\"varint\", \"bits\" or \"huff\")")
     if chroma_symbols is not None and len(chroma_symbols) != len(symbols):
         raise ValueError(f"{len(chroma_symbols)} chroma frames against {len(symbols)} luma frames")
 
@@ -180,6 +184,8 @@ def open_frames(path):
         lens = np.frombuffer(take(2 * nb), np.uint16)
         if int(lens.astype(np.int64).sum()) != nbytes:
             raise ValueError(f"{name}: {what} lengths do not add up to the frame's byte count")
+        if coding == "huff" and nb and int(lens[0]) < HUFF_TABLE_BYTES[what]:
+            raise ValueError(f"{name}: the first {what} is shorter than the frame's Huffman tables")
         return lens, take(nbytes)
 
     def frames():
@@ -213,7 +219,7 @@ def open_frames(path):
 def read(path: str, device) -> dict:
     """-> {"h", "w", "bs", "nb", "coding", "frame_types", "qp_rows", "packed": [device uint8],
     "offs": [device int32 [nb + 1]], "layout", "qp_maps", "chroma_packed", "chroma_offs",
-    "chroma_qp_offset"}.  "coding" is "varint" or "bits".  In layout 1: "qp_maps" holds per frame
+    "chroma_qp_offset"}.  "coding" is "varint", "bits" or "huff".  In layout 1: "qp_maps" holds per frame
     a device int32 [nb] or None (None itself when the file carries no maps), "chroma_packed" /
     "chroma_offs" the chroma streams like "packed" / "offs" (None without chroma); in layout 0
     all four are None."""
@@ -243,6 +249,8 @@ def read(path: str, device) -> dict:
         np.cumsum(lens, out=o[1:])
         if o[-1] != nbytes:
             raise ValueError(f"{path}: {what} lengths do not add up to the frame's byte count")
+        if coding == "huff" and nb and int(lens[0]) < HUFF_TABLE_BYTES[what]:
+            raise ValueError(f"{path}: the first {what} is shorter than the frame's Huffman tables")
         if p + nbytes > len(data):
             raise ValueError(f"{path}: the file ends inside a frame")
         return (p + nbytes, torch.from_numpy(o.astype(np.int32)).to(device),

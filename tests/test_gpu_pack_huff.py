@@ -1,0 +1,388 @@
+"""so_pack_frames_huff / so_unpack_frames_huff on the GPU against the plain-Python model of the
+"huff" coding (tests/packhuffref.py): the edge corpus (tests/packbitcases.py) and the CIF goldens
+byte for byte, the launch geometry, the capacity guard, per-frame tables, every malformed rule
+(tests/packhuffcases.py); then the public paths (transmit_packed / transmit_packed420 with
+coding="huff", decode_packed_file / decode_packed_stream, HostStreamEncoder).  Every output buffer
+starts as a sentinel and ends in a guard region; every comparison is exact equality."""
+import ctypes
+import os
+from functools import lru_cache
+
+import numpy as np
+import pytest
+import torch
+
+import packbitcases
+import packhuffcases as C
+import packhuffref as H
+from conftest import golden
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 4096                                     # bytes past `cap` in out; > one block's bound
+TAIL = 16                                        # guard elements past every other output row
+OUT_FILL, OFFS_FILL, SPLIT_FILL, I16_FILL = 0xAB, 0x5A5A5A5A, 0xEE, 0x7B7B
+NBS = (1, 2, 63, 64, 65, 257)                    # the wave loop (8 blocks a wave, two per iteration) and a second workgroup
+
+
+def _lib():
+    from streamoptima_amd import _lib as m
+    return m.load(), m
+
+
+def _ptrs(ts):
+    return (ctypes.c_void_p * len(ts))(*[t if isinstance(t, int) else t.data_ptr() for t in ts])
+
+
+def _dev(a, gpu):
+    return torch.from_numpy(np.array(a, order="C")).to(gpu)      # a copy: corpus arrays are read-only
+
+
+@lru_cache(maxsize=None)
+def _frame(kind, ftype, idx):
+    """Blocks idx (a tuple) of a corpus as one frame -> ((ftype, split, mv, qtc), the model's bytes
+    per block -- computed once and shared, the tables being the frame's own)."""
+    split, mv, qtc = packbitcases.corpus(kind, ftype)
+    i = np.array(idx)
+    f = (ftype, split[i], mv[i], qtc[i])
+    return f, H.pack_blocks_huff(f[1], f[2], f[3], packbitcases.block_size(kind), ftype)
+
+
+def _varied_frames(kind, nframes, nb):
+    """nframes frames of nb blocks: different content, frame types mixed in one call."""
+    n = packbitcases.corpus(kind, 0)[0].size
+    return [_frame(kind, (i + nb) % 2, tuple((i * 37 + 11 * nb + np.arange(nb)) % n)) for i in range(nframes)]
+
+
+def _pack(gpu, frames, bs, cap, totals=True):
+    """so_pack_frames_huff on [(ftype, split, mv, qtc)] -> offs [n, nb + 1 + TAIL], out
+    [n, cap + GUARD], totals [n + 2], as numpy."""
+    lib, m = _lib()
+    n, nb = len(frames), frames[0][1].size
+    dev = [[_dev(a, gpu) for a in f[1:]] for f in frames]
+    offs = torch.full((n, nb + 1 + TAIL), OFFS_FILL, dtype=torch.int32, device=gpu)
+    out = torch.full((n, cap + GUARD), OUT_FILL, dtype=torch.uint8, device=gpu)
+    tot = torch.full((n + 2,), OFFS_FILL, dtype=torch.int32, device=gpu)
+    rc = lib.so_pack_frames_huff(n, (ctypes.c_int32 * n)(*[f[0] for f in frames]), _ptrs([d[0] for d in dev]),
+                                 _ptrs([d[1] for d in dev]), _ptrs([d[2] for d in dev]), nb, bs, _ptrs(list(offs)),
+                                 _ptrs(list(out)), cap, tot.data_ptr() + 4 if totals else None, m.stream_handle(gpu))
+    m.check(rc, "so_pack_frames_huff")
+    torch.cuda.synchronize()
+    return offs.cpu().numpy(), out.cpu().numpy(), tot.cpu().numpy()
+
+
+def _offsets(blk):
+    return np.concatenate(([0], np.cumsum([len(x) for x in blk])))
+
+
+def _check_pack(offs, out, tot, blocks, cap, totals=True):
+    """offs complete whatever the cap; exactly the blocks with offs[b + 1] <= cap written,
+    byte-exact; the sentinel everywhere else, guards included."""
+    for i, blk in enumerate(blocks):
+        nb = len(blk)
+        want_offs = _offsets(blk)
+        assert np.array_equal(offs[i, :nb + 1], want_offs), (i, np.flatnonzero(offs[i, :nb + 1] != want_offs)[:8])
+        assert (offs[i, nb + 1:] == OFFS_FILL).all(), i
+        fit = int(want_offs[want_offs <= cap].max())          # offsets ascend: a prefix fits
+        want = np.full(out.shape[1], OUT_FILL, np.uint8)
+        want[:fit] = np.frombuffer(b"".join(blk), np.uint8)[:fit]
+        assert np.array_equal(out[i], want), (i, np.flatnonzero(out[i] != want)[:8])
+        if totals:
+            assert tot[i + 1] == want_offs[-1], i
+    assert tot[0] == OFFS_FILL and tot[-1] == OFFS_FILL
+    if not totals:
+        assert (tot == OFFS_FILL).all()
+
+
+def _cap_for(blocks):
+    return max(sum(len(x) for x in blk) for blk in blocks) + 64
+
+
+class _Unpack:
+    """so_unpack_frames_huff on streams that share one device buffer; outputs poisoned, each row
+    with TAIL guard elements.  launch() is asynchronous; fetch() synchronises."""
+
+    def __init__(self, gpu, streams, offs, nb, bs, ncalls=1):
+        self.gpu, self.nb, self.bs, n = gpu, nb, bs, len(streams)
+        starts = np.concatenate(([0], np.cumsum([len(s) for s in streams])))
+        self.packed = _dev(np.frombuffer(b"".join(streams) + b"\xff" * 64, np.uint8), gpu)
+        self.in_ptr = [self.packed.data_ptr() + int(s) for s in starts[:-1]]
+        self.offs = _dev(np.asarray(offs, np.int32).reshape(n, nb + 1), gpu)
+        self.split = torch.full((n, nb + TAIL), SPLIT_FILL, dtype=torch.uint8, device=gpu)
+        self.mv = torch.full((n, nb * 12 + TAIL), I16_FILL, dtype=torch.int16, device=gpu)
+        self.qtc = torch.full((n, nb * bs * bs + TAIL), I16_FILL, dtype=torch.int16, device=gpu)
+        self.err = torch.zeros(ncalls, dtype=torch.int32, device=gpu)
+        self.rows = [self.offs.data_ptr(), self.split.data_ptr(), self.mv.data_ptr(), self.qtc.data_ptr()]
+        self.stride = [t.stride(0) * t.element_size() for t in (self.offs, self.split, self.mv, self.qtc)]
+
+    def launch(self, frames, ftypes, call=0):
+        lib, m = _lib()
+        n = len(frames)
+        row = lambda k: _ptrs([self.rows[k] + f * self.stride[k] for f in frames])   # noqa: E731
+        rc = lib.so_unpack_frames_huff(n, (ctypes.c_int32 * n)(*ftypes), _ptrs([self.in_ptr[f] for f in frames]),
+                                       row(0), self.nb, self.bs, row(1), row(2), row(3),
+                                       self.err.data_ptr() + 4 * call, m.stream_handle(self.gpu))
+        m.check(rc, "so_unpack_frames_huff")
+
+    def fetch(self):
+        torch.cuda.synchronize()
+        return self.split.cpu().numpy(), self.mv.cpu().numpy(), self.qtc.cpu().numpy(), self.err.cpu().numpy()
+
+
+def _expected_rows(ftype, split, mv, qtc):
+    """One frame's output rows as _Unpack lays them out: untouched elements keep the poison."""
+    nb = split.size
+    assert I16_FILL not in mv and I16_FILL not in qtc      # an unwritten element cannot pass
+    w = 12 if ftype == 1 else 4
+    s = np.full(nb + TAIL, SPLIT_FILL, np.uint8)
+    s[:nb] = split
+    m = np.full(nb * 12 + TAIL, I16_FILL, np.int16)
+    m[:nb * w] = packbitcases.used_mv(split, mv).reshape(-1)
+    q = np.full(qtc.size + TAIL, I16_FILL, np.int16)
+    q[:qtc.size] = qtc.reshape(-1)
+    return s, m, q
+
+
+def _check_unpack(got, frames):
+    split, mv, qtc, err = got
+    assert err.tolist() == [0] * err.size
+    for i, (ftype, sp, m, q) in enumerate(frames):
+        ws, wm, wq = _expected_rows(ftype, sp, m, q)
+        assert np.array_equal(split[i], ws), i
+        assert np.array_equal(mv[i], wm), (i, np.flatnonzero(mv[i] != wm)[:8])
+        assert np.array_equal(qtc[i], wq), (i, np.flatnonzero(qtc[i] != wq)[:8])
+
+
+# ---- the packer against the model's writer --------------------------------------------------------
+@pytest.mark.parametrize("ftype", [0, 1])
+@pytest.mark.parametrize("kind", packbitcases.KINDS)
+def test_pack_huff_corpus_bytes_exact(gpu, kind, ftype):
+    """Every corpus as one frame: tables, bytes, offsets and the total equal the model's (null
+    totals: the same bytes); then so_unpack_frames_huff inverts the kernel's own stream and the
+    model's, outputs poisoned first."""
+    bs = packbitcases.block_size(kind)
+    n = packbitcases.corpus(kind, ftype)[0].size
+    frame, blk = _frame(kind, ftype, tuple(range(n)))
+    cap = _cap_for([blk])
+    offs, out, tot = _pack(gpu, [frame], bs, cap)
+    _check_pack(offs, out, tot, [blk], cap)
+    offs2, out2, tot2 = _pack(gpu, [frame], bs, cap, totals=False)
+    _check_pack(offs2, out2, tot2, [blk], cap, totals=False)
+    own = out[0, :int(offs[0, n])].tobytes()
+    u = _Unpack(gpu, [own, b"".join(blk)], [offs[0, :n + 1], _offsets(blk)], n, bs)
+    u.launch([0, 1], [ftype, ftype])
+    _check_unpack(u.fetch(), [frame, frame])
+
+
+@pytest.mark.parametrize("nframes,nbs", [(1, NBS), (3, (2, 65))])
+@pytest.mark.parametrize("kind", packbitcases.KINDS)
+def test_pack_huff_launch_geometry(gpu, kind, nframes, nbs):
+    """nb across the wave loop and the workgroup, 1 and 3 frames a call (frame types mixed, split
+    on and off by the kind): every frame's own tables, the model's bytes, and the round trip."""
+    bs = packbitcases.block_size(kind)
+    for nb in nbs:
+        frames, blocks = zip(*_varied_frames(kind, nframes, nb))
+        cap = _cap_for(blocks)
+        offs, out, tot = _pack(gpu, list(frames), bs, cap)
+        _check_pack(offs, out, tot, blocks, cap)
+        u = _Unpack(gpu, [b"".join(blk) for blk in blocks], [_offsets(blk) for blk in blocks], nb, bs)
+        u.launch(list(range(nframes)), [f[0] for f in frames])
+        _check_unpack(u.fetch(), frames)
+
+
+@pytest.mark.parametrize("name,ft", [("cif_p_vbs0", 1), ("cif_i_qp6_vbs0", 0), ("cif_p_vbs1", 1)])
+def test_pack_huff_cif_goldens_bytes_exact(gpu, name, ft):
+    g = golden(name + ".npz")
+    frame = (ft, g["split"], g["mv"], g["qtc"])
+    blk = H.pack_blocks_huff(g["split"], g["mv"], g["qtc"], 16, ft)
+    cap = _cap_for([blk])
+    offs, out, tot = _pack(gpu, [frame], 16, cap)
+    _check_pack(offs, out, tot, [blk], cap)
+    nb = g["split"].size
+    u = _Unpack(gpu, [out[0, :int(offs[0, nb])].tobytes()], [offs[0, :nb + 1]], nb, 16)
+    u.launch([0], [ft])
+    _check_unpack(u.fetch(), [frame])
+
+
+def test_pack_huff_capacity_guard_edges(gpu):
+    nb, k = 64, 32
+    n = packbitcases.corpus("m16", 1)[0].size
+    frame, blk = _frame("m16", 1, tuple(np.linspace(0, n - 1, nb).astype(int)))
+    o = _offsets(blk)
+    total = int(o[nb])
+    # block 0 holds the tables: a capacity below it writes nothing, not even the tables
+    for cap in (0, int(o[1]) - 1, int(o[1]), int(o[k]) - 1, int(o[k]), int(o[k]) + 1, total - 1, total):
+        offs, out, tot = _pack(gpu, [frame], 16, cap)
+        _check_pack(offs, out, tot, [blk], cap)
+
+
+def test_pack_huff_tables_are_per_frame(gpu):
+    """An all-zero frame next to a noise frame (and a second all-zero one) in one call: each gets
+    the tables of its own statistics."""
+    nb = 65
+    rng = np.random.default_rng(7)
+    zero = (1, np.zeros(nb, np.uint8), np.zeros((nb, 4, 3), np.int16), np.zeros((nb, 256), np.int16))
+    noise = (1, rng.integers(0, 2, nb).astype(np.uint8), rng.integers(-40, 40, (nb, 4, 3)).astype(np.int16),
+             (rng.integers(-60, 60, (nb, 256)) * (rng.random((nb, 256)) < 0.3)).astype(np.int16))
+    frames = [zero, noise, zero]
+    blocks = [H.pack_blocks_huff(f[1], f[2], f[3], 16, 1) for f in frames]
+    T = H.LUMA_TABLE_BYTES
+    assert blocks[0][0][:T] != blocks[1][0][:T] and [len(b) for b in blocks[0]] == [T + 1] + [1] * (nb - 1)
+    cap = _cap_for(blocks)
+    offs, out, tot = _pack(gpu, frames, 16, cap)
+    _check_pack(offs, out, tot, blocks, cap)
+    u = _Unpack(gpu, [b"".join(blk) for blk in blocks], [_offsets(blk) for blk in blocks], nb, 16)
+    u.launch([0, 1, 2], [1, 1, 1])
+    _check_unpack(u.fetch(), frames)
+
+
+# ---- damaged and non-canonical input: the unpacker against the strict model -------------------------
+def test_unpack_huff_agrees_with_strict_model(gpu):
+    """Every hand-made case of packhuffcases: err == 1 + the block the model calls malformed, else
+    err == 0 and the outputs are the frame's; one err word per case."""
+    split, mv, qtc = C.small_frame()
+    cases = C.all_cases()
+    nb = 6
+    for name, blocks, bad in cases:
+        assert H.verdict(H.unpack_blocks_huff_strict, blocks, 16, 1)[0] == ("ok" if bad is None else "bad"), name
+    u = _Unpack(gpu, [b"".join(b) for _, b, _ in cases], [_offsets(b) for _, b, _ in cases], nb, 16, ncalls=len(cases))
+    for c in range(len(cases)):
+        u.launch([c], [1], call=c)
+    s, m, q, err = u.fetch()
+    ws, wm, wq = _expected_rows(1, split, mv, qtc)
+    for c, (name, _, bad) in enumerate(cases):
+        assert int(err[c]) == (0 if bad is None else bad + 1), (name, int(err[c]))
+        if bad is None:
+            assert np.array_equal(s[c], ws) and np.array_equal(m[c], wm) and np.array_equal(q[c], wq), name
+        elif bad != 0 or name not in ("kraft above 1", "spare nibble", "short tables", "empty block 0"):
+            keep = np.arange(nb) != bad                     # the other blocks decode as in the valid frame
+            assert np.array_equal(s[c, :nb][keep], split[keep]), name
+            assert np.array_equal(q[c, :nb * 256].reshape(nb, 256)[keep], qtc[keep]), name
+    # reversed offsets, both inside the stream
+    good = cases[0][1]
+    rev = _offsets(good).copy()
+    rev[3] = rev[2] - 1
+    blocks8, bad8 = C.split_at_bs8()
+    u = _Unpack(gpu, [b"".join(good)], [rev], nb, 16)
+    u.launch([0], [1])
+    assert int(u.fetch()[3][0]) - 1 in (2, 3)
+    u = _Unpack(gpu, [blocks8[0]], [_offsets(blocks8)], 1, 8)
+    u.launch([0], [1])
+    assert int(u.fetch()[3][0]) == bad8 + 1
+
+
+def test_unpack_huff_single_block_mutants(gpu):
+    """Every single-bit flip of the code bytes of one-block frames (and a sample of the table
+    bytes), the last byte cut, a byte appended: err != 0 exactly when the model calls it malformed."""
+    split, mv, qtc = C.small_frame()
+    streams, want = [], []
+    for b in (0, 1, 5):
+        base = H.pack_blocks_huff(split[b:b + 1], mv[b:b + 1], qtc[b:b + 1], 16, 1)[0]
+        T = H.LUMA_TABLE_BYTES
+        muts = [base, base[:-1], base + b"\x00", base + b"\x80"]
+        for bit in list(range(8 * T, 8 * len(base))) + list(range(0, 8 * T, 41)):
+            raw = bytearray(base)
+            raw[bit >> 3] ^= 0x80 >> (bit & 7)
+            muts.append(bytes(raw))
+        for data in muts:
+            streams.append(data)
+            want.append(H.verdict(H.unpack_blocks_huff_strict, [data], 16, 1))
+    assert sum(k == "ok" for k, _ in want) > 20 and sum(k == "bad" for k, _ in want) > 20
+    u = _Unpack(gpu, streams, [[0, len(s)] for s in streams], 1, 16, ncalls=len(streams))
+    for c in range(len(streams)):
+        u.launch([c], [1], call=c)
+    s, m, q, err = u.fetch()
+    for c, (kind, res) in enumerate(want):
+        assert (int(err[c]) != 0) == (kind == "bad"), (c, int(err[c]), kind)
+        if kind == "ok":
+            assert s[c, 0] == res["split"][0] and np.array_equal(q[c, :256], res["qtc"][0])
+            assert np.array_equal(m[c, :12], res["mv"][0].reshape(-1))
+
+
+# ---- the public paths --------------------------------------------------------------------------------
+def _rc_kw():
+    import json
+    from conftest import GOLDEN
+    tables = json.load(open(os.path.join(GOLDEN, "rc_schedule.json")))["tables"]
+    return dict(RCFlag=1, targetBR="2 mbps", qp_rate_tables=tables)
+
+
+@pytest.mark.parametrize("case", ["vbs_64x128", "cif_p_rc1"])
+def test_transmit_packed_huff_then_decode(gpu, tmp_path, monkeypatch, case):
+    """transmit_packed(coding="huff") -> decode_packed_file gives the frames of the varint file; the
+    file says coding 3 and its payload is what the host decoder reads."""
+    from streamoptima_amd import bitstream, packedfile
+    from streamoptima_amd.Encoder import Y_Video_codec
+    from streamoptima_amd.decoder import decoder
+    from streamoptima_amd.synth import synth_sequence
+    monkeypatch.chdir(tmp_path)
+    h, w, frames, vbs, kw = (64, 128, 4, True, {}) if case == "vbs_64x128" else (288, 352, 4, False, _rc_kw())
+    seq = synth_sequence(frames, h, w, seed=31)
+    enc = Y_Video_codec(h, w, frames, 16, 16, 4, frames, 0, 0.015, vbs, y_only_frame_arr=seq, device=gpu, **kw)
+    enc.encode()
+    p1, p2, p3 = (str(tmp_path / f"gop_v{i}.sopk") for i in (1, 2, 3))
+    size1 = enc.transmit_packed(p1)
+    size2 = enc.transmit_packed(p2, coding="bits")
+    size3 = enc.transmit_packed(p3, coding="huff")
+    assert size3 == os.path.getsize(p3)
+    print(case, "varint", size1, "bits", size2, "huff", size3)
+    meta = packedfile.read(p3, gpu)
+    assert meta["coding"] == "huff"
+    dec = decoder(0, frames, 16, frames, h, w, 4, 1, False, 0.015, vbs, device=gpu, **kw)
+    out1 = dec.decode_packed_file(p1)
+    out3 = dec.decode_packed_file(p3)
+    for i in range(frames):
+        assert (out1[i] == out3[i]).all(), i
+        sym = enc._symbols[i]
+        got = bitstream.unpack_frame_huff(meta["packed"][i].cpu().numpy(), sym.split.numel(), 16, sym.frame_type)
+        assert np.array_equal(got["qtc"], sym.qtc.cpu().numpy().reshape(got["qtc"].shape)), i
+
+
+def test_transmit_packed420_huff_stream_and_host_encoder(gpu, tmp_path, monkeypatch):
+    """4:2:0, two I-frames in the GOP: transmit_packed420(coding="huff") -> decode_packed_stream gives
+    Y, U and V of the varint file (a fused stream decoder takes the unpack path for such a file); a
+    HostStreamEncoder(coding="huff", lengths=True) result written by write_packed is that file byte
+    for byte, and so is a coding="bits" one against transmit_packed420(coding="bits")."""
+    from streamoptima_amd import packedfile
+    from streamoptima_amd.Encoder import Y_Video_codec
+    from streamoptima_amd.decoder import decoder
+    from streamoptima_amd.hoststream import HostStreamEncoder
+    from streamoptima_amd.synth import synth_sequence
+    monkeypatch.chdir(tmp_path)
+    h, w, frames, intra = 64, 128, 5, 3
+    y = synth_sequence(frames, h, w, seed=9)
+    uv = np.stack([synth_sequence(frames, h // 2, w // 2, seed=109), synth_sequence(frames, h // 2, w // 2, seed=209)],
+                  axis=1)
+    enc = Y_Video_codec(h, w, frames, 16, 16, 4, intra, 0, 0.015, True, y_only_frame_arr=y, device=gpu, chroma=True,
+                        chroma_qp_offset=1, uv_frame_arr=uv)
+    enc.encode()
+    paths = {c: str(tmp_path / f"{c}.sopk") for c in ("varint", "bits", "huff")}
+    for c, p in paths.items():
+        enc.transmit_packed420(p, coding=c)
+    assert packedfile.read(paths["huff"], gpu)["coding"] == "huff"
+    got = {}
+    for c in ("varint", "huff"):
+        dec = decoder(0, intra, 16, frames, h, w, 4, 1, False, 0.015, True, device=gpu)
+        out = []
+        info = dec.decode_packed_stream(paths[c], consume=lambda i, yy, u, v, out=out: out.append(
+            (np.array(yy), np.array(u), np.array(v))))
+        assert info["coding"] == c and info["frames"] == frames
+        got[c] = out
+    for i in range(frames):
+        for a, b in zip(got["varint"][i], got["huff"][i]):
+            assert np.array_equal(a, b), i
+        assert np.array_equal(got["huff"][i][0], enc._symbols[i].recon.cpu().numpy()[:h, :w]), i
+    dec = decoder(0, intra, 16, frames, h, w, 4, 1, False, 0.015, True, device=gpu)
+    out = dec.decode_packed_file(paths["huff"])
+    for i in range(frames):
+        assert np.array_equal(out[i], got["varint"][i][0]), i
+        assert np.array_equal(dec.decoded_chroma[i][0], got["varint"][i][1]), i
+    y_host = enc._upload_padded(y).cpu().pin_memory()
+    uv_host = enc._upload_uv_padded(uv).cpu().pin_memory()
+    for c in ("huff", "bits"):
+        hs = HostStreamEncoder(enc, frames, chunk=2, lengths=True, coding=c)
+        streamed = str(tmp_path / f"streamed_{c}.sopk")
+        hs.write_packed(streamed, hs.encode(y_host, intra, uv_host=uv_host))
+        assert open(streamed, "rb").read() == open(paths[c], "rb").read(), c
+    with pytest.raises(ValueError):
+        HostStreamEncoder(enc, frames, coding="nope")
