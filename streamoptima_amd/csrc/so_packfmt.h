@@ -7,7 +7,8 @@
 //   * the plain layer -- C++17 with no device builtin beyond __builtin_clz*, every function SO_DEV:
 //     the launch interface (frame structs, bounds, *_launch prototypes), the coding primitives, the
 //     scan tables, and the strict decoders (two readers over a record's bytes, one token-list
-//     parser, the luma and chroma record bodies).  A host compiler can include it with SO_DEV
+//     parser, the luma and chroma record bodies; for "huff" the table rule, the expanded tables, the
+//     reader through them and its two record bodies).  A host compiler can include it with SO_DEV
 //     defined as `inline` (tests/host/unpack_check.cpp runs the decoders under sanitizers);
 //   * the device layer (hipcc only) -- what the pack kernels share: the wave scan, the LDS stages,
 //     the run machinery, the order-k choice, the load-ahead loop and the host loop over frames.
@@ -303,6 +304,126 @@ SO_DEV void unpack_chroma_record(Reader& r, int16_t* qu, int16_t* qv) {
     const int k = r.order();
     unpack_token_list(qu, scan_table(8), 64, r, k);
     if (!r.bad) unpack_token_list(qv, scan_table(8), 64, r, k);
+    r.finish();
+}
+
+// ---- the strict decoder of the "huff" coding ----------------------------------------------------
+// The contexts: cls(p) = min(bit_length(p), 6).
+SO_DEV int huff_cls(int p) { return p == 0 ? 0 : (32 - __builtin_clz((unsigned)p) < 6 ? 32 - __builtin_clz((unsigned)p) : 6); }
+
+// A table as a decoder holds it: per length the first canonical code, the number of codes and where
+// its symbols start in `sym` (the symbols by (length, symbol)).  Built from the transmitted lengths
+// alone; any lengths whose Kraft sum is <= 1 are a valid table.
+struct HuffDec {
+    uint16_t first[kHuffMaxLen + 1];
+    uint8_t cnt[kHuffMaxLen + 1], base[kHuffMaxLen + 1];
+    uint8_t sym[kHuffSyms];
+};
+
+SO_DEV int huff_nibble(const uint8_t* bytes, int i) { return i & 1 ? bytes[i >> 1] & 15 : bytes[i >> 1] >> 4; }
+
+// The frame-level rule, first half: record 0, n bytes at `bytes`, holds the table bytes of ntab tables
+// and their spare nibble (luma: 645 nibbles in 323 bytes) is 0.  Reads the spare nibble's byte only
+// when record 0 holds it.
+SO_DEV bool huff_tables_head_ok(const uint8_t* bytes, unsigned long long n, int ntab) {
+    if (n < (unsigned long long)huff_table_bytes(ntab)) return false;
+    const int nnib = ntab * kHuffSyms;
+    return !(nnib & 1) || huff_nibble(bytes, nnib) == 0;
+}
+
+// Second half: table t of the table bytes; false when its Kraft sum exceeds 1.  Reads the table's 43
+// nibbles, writes d.
+SO_DEV bool huff_dec_build(HuffDec& d, const uint8_t* bytes, int t) {
+    for (int l = 0; l <= kHuffMaxLen; ++l) d.cnt[l] = 0;
+    for (int s = 0; s < kHuffSyms; ++s) ++d.cnt[huff_nibble(bytes, t * kHuffSyms + s)];
+    d.cnt[0] = 0;
+    uint32_t kraft = 0, code = 0, at = 0;
+    for (int l = 1; l <= kHuffMaxLen; ++l) {
+        kraft += (uint32_t)d.cnt[l] << (kHuffMaxLen - l);
+        d.first[l] = (uint16_t)code;
+        d.base[l] = (uint8_t)at;
+        code = (code + d.cnt[l]) << 1;
+        at += d.cnt[l];
+    }
+    if (kraft > (1u << kHuffMaxLen)) return false;
+    for (int l = 1, n = 0; l <= kHuffMaxLen; ++l)
+        for (int s = 0; s < kHuffSyms && d.cnt[l]; ++s)
+            if (huff_nibble(bytes, t * kHuffSyms + s) == l) d.sym[n++] = (uint8_t)s;
+    return true;
+}
+
+// The bit reader with values read through the tables.  val(t): a bit pattern that matches no code of
+// table t, or a code or its raw bits running past the record's last byte, is malformed.
+struct HuffReader : BitReader {
+    const HuffDec* tabs;
+    SO_DEV HuffReader(const uint8_t* q, size_t n, bool bad0, const HuffDec* t) : BitReader(q, n, bad0), tabs(t) {}
+    SO_DEV int val(int t) {
+        const HuffDec& d = tabs[t];
+        const unsigned long long W = peek();
+        const uint32_t top = (uint32_t)(W >> (64 - kHuffMaxLen));
+        int len = 1, s = -1;
+        for (; len <= kHuffMaxLen; ++len) {
+            const uint32_t c = (top >> (kHuffMaxLen - len)) - d.first[len];
+            if (c < d.cnt[len]) {
+                s = d.sym[d.base[len] + c];
+                break;
+            }
+        }
+        uint32_t z = (uint32_t)s;
+        int nx = 0;
+        if (s >= 32) {
+            nx = s - 27;
+            z = (1u << nx) | (uint32_t)((W << len) >> (64 - nx));
+        }
+        if (s < 0 || pos + len + nx > nbits) {
+            bad = true;
+            return 0;
+        }
+        pos += len + nx;
+        return unzz(z);
+    }
+};
+
+// unpack_token_list with the tables picked by position; TOK0: the first token table
+template <int TOK0>
+SO_DEV void unpack_huff_list(int16_t* q, const uint8_t* scan, int nn, HuffReader& r) {
+    int c = 0;
+    while (c < nn && !r.bad) {
+        const int t = r.val(TOK0 + huff_cls(c));
+        if (r.bad) break;
+        if (t < 0) {
+            if (-t > nn - c) { r.bad = true; break; }
+            for (int i = 0; i < -t && !r.bad; ++i) q[scan[c + i]] = (int16_t)r.val(TOK0 + kHuffCtx + huff_cls(c + i));
+            c -= t;
+        } else if (t == 0) {
+            break;
+        } else {
+            if (t > nn - c) { r.bad = true; break; }
+            c += t;
+        }
+    }
+}
+
+// One luma record (record 0: what follows the table bytes): split (1 raw bit; 1 only at block size
+// 16), the mv values through table 0, then 1 list of BS x BS or 4 of 8 x 8 through tok0..6 (tables
+// 1..7) and coef0..6.  mv and q as unpack_luma_record.
+template <int BS>
+SO_DEV void unpack_huff_luma_record(HuffReader& r, int inter, uint8_t* split, int16_t* mv, int16_t* q) {
+    const int sp = r.split();
+    if (sp != 0 && BS != 16) r.bad = true;
+    *split = (uint8_t)(sp == 1 && !r.bad);
+    const int per = inter ? 3 : 1, nmv = (sp == 1 ? 4 : 1) * per;
+    for (int j = 0; j < 4 * per; ++j) mv[j] = (int16_t)(j < nmv && !r.bad ? r.val(0) : 0);
+    const int nsub = sp == 1 ? 4 : 1, n = sp == 1 ? 8 : BS, nn = n * n;
+    const uint8_t* scan = scan_table(n);
+    for (int j = 0; j < nsub && !r.bad; ++j) unpack_huff_list<1>(q + j * nn, scan, nn, r);
+    r.finish();
+}
+
+// One chroma record: U's 8 x 8 list, then V's, through tok0..6 (tables 0..6) and coef0..6.
+SO_DEV void unpack_huff_chroma_record(HuffReader& r, int16_t* qu, int16_t* qv) {
+    unpack_huff_list<0>(qu, scan_table(8), 64, r);
+    if (!r.bad) unpack_huff_list<0>(qv, scan_table(8), 64, r);
     r.finish();
 }
 

@@ -24,8 +24,7 @@
 
 namespace so {
 
-// ---- the value mapping and the contexts -------------------------------------------------------
-SO_DEV int huff_cls(int p) { return p == 0 ? 0 : (32 - __builtin_clz((unsigned)p) < 6 ? 32 - __builtin_clz((unsigned)p) : 6); }
+// ---- the value mapping (the contexts: so_packfmt.h huff_cls) -----------------------------------
 // symbol of z <= 65535; *nx = the raw bits that follow its code
 SO_DEV int huff_sym(uint32_t z, int* nx) {
     if (z < 32u) {
@@ -354,103 +353,22 @@ __global__ void __launch_bounds__(256) pack_chroma_huff_kernel(const ChromaPackA
 }
 
 // ---- unpack --------------------------------------------------------------------------------------
-// A table as a decoder holds it: per length the first canonical code, the number of codes and where
-// its symbols start in `sym` (the symbols by (length, symbol)).  Built from the transmitted lengths
-// alone; any lengths whose Kraft sum is <= 1 are a valid table.
-struct HuffDec {
-    uint16_t first[kHuffMaxLen + 1];
-    uint8_t cnt[kHuffMaxLen + 1], base[kHuffMaxLen + 1];
-    uint8_t sym[kHuffSyms];
-};
-
-SO_DEV int huff_nibble(const uint8_t* bytes, int i) { return i & 1 ? bytes[i >> 1] & 15 : bytes[i >> 1] >> 4; }
-
-// table t of the table bytes; false when its Kraft sum exceeds 1
-SO_DEV bool huff_dec_build(HuffDec& d, const uint8_t* bytes, int t) {
-    for (int l = 0; l <= kHuffMaxLen; ++l) d.cnt[l] = 0;
-    for (int s = 0; s < kHuffSyms; ++s) ++d.cnt[huff_nibble(bytes, t * kHuffSyms + s)];
-    d.cnt[0] = 0;
-    uint32_t kraft = 0, code = 0, at = 0;
-    for (int l = 1; l <= kHuffMaxLen; ++l) {
-        kraft += (uint32_t)d.cnt[l] << (kHuffMaxLen - l);
-        d.first[l] = (uint16_t)code;
-        d.base[l] = (uint8_t)at;
-        code = (code + d.cnt[l]) << 1;
-        at += d.cnt[l];
-    }
-    if (kraft > (1u << kHuffMaxLen)) return false;
-    for (int l = 1, n = 0; l <= kHuffMaxLen; ++l)
-        for (int s = 0; s < kHuffSyms && d.cnt[l]; ++s)
-            if (huff_nibble(bytes, t * kHuffSyms + s) == l) d.sym[n++] = (uint8_t)s;
-    return true;
-}
+// The decoder itself -- the tables' rule, HuffDec, HuffReader, the list parser and the two record
+// bodies -- is the plain layer of so_packfmt.h; here only the workgroup's cooperation around it.
 
 // The frame's tables, by the whole workgroup: false (the frame is malformed at record 0) when
-// record 0 is shorter than the table bytes, a table's Kraft sum exceeds 1 or the last nibble is set.
-// Reads nothing but the table bytes, and those only when record 0 holds them.
+// record 0 is shorter than the table bytes, the last nibble is set (huff_tables_head_ok) or a
+// table's Kraft sum exceeds 1 (huff_dec_build, lane t for table t).  Reads nothing but the table
+// bytes, and those only when record 0 holds them.
 SO_DEV bool huff_dec_tables(HuffDec* tabs, int* bad, const uint8_t* in, const uint32_t* offs, int ntab) {
     const uint32_t o0 = offs[0], o1 = offs[1];
     const bool fits = o1 >= o0 && o1 - o0 >= (uint32_t)huff_table_bytes(ntab);
-    const int nnib = ntab * kHuffSyms;   // odd for luma: one spare nibble
-    if (threadIdx.x == 0) *bad = !fits || ((nnib & 1) && huff_nibble(in + o0, nnib) != 0);
+    if (threadIdx.x == 0) *bad = !fits || !huff_tables_head_ok(in + o0, o1 - o0, ntab);
     __syncthreads();
     if (fits && (int)threadIdx.x < ntab && !huff_dec_build(tabs[threadIdx.x], in + o0, threadIdx.x))
         __hip_atomic_store(bad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     __syncthreads();
     return *bad == 0;
-}
-
-// The bit reader of so_packfmt.h with values read through the tables.  val(t): a bit pattern that
-// matches no code of table t, or a code or its raw bits running past the record's last byte, is
-// malformed.
-struct HuffReader : BitReader {
-    const HuffDec* tabs;
-    SO_DEV HuffReader(const uint8_t* q, size_t n, bool bad0, const HuffDec* t) : BitReader(q, n, bad0), tabs(t) {}
-    SO_DEV int val(int t) {
-        const HuffDec& d = tabs[t];
-        const unsigned long long W = peek();
-        const uint32_t top = (uint32_t)(W >> (64 - kHuffMaxLen));
-        int len = 1, s = -1;
-        for (; len <= kHuffMaxLen; ++len) {
-            const uint32_t c = (top >> (kHuffMaxLen - len)) - d.first[len];
-            if (c < d.cnt[len]) {
-                s = d.sym[d.base[len] + c];
-                break;
-            }
-        }
-        uint32_t z = (uint32_t)s;
-        int nx = 0;
-        if (s >= 32) {
-            nx = s - 27;
-            z = (1u << nx) | (uint32_t)((W << len) >> (64 - nx));
-        }
-        if (s < 0 || pos + len + nx > nbits) {
-            bad = true;
-            return 0;
-        }
-        pos += len + nx;
-        return unzz(z);
-    }
-};
-
-// unpack_token_list with the tables picked by position; TOK0: the first token table
-template <int TOK0>
-SO_DEV void unpack_huff_list(int16_t* q, const uint8_t* scan, int nn, HuffReader& r) {
-    int c = 0;
-    while (c < nn && !r.bad) {
-        const int t = r.val(TOK0 + huff_cls(c));
-        if (r.bad) break;
-        if (t < 0) {
-            if (-t > nn - c) { r.bad = true; break; }
-            for (int i = 0; i < -t && !r.bad; ++i) q[scan[c + i]] = (int16_t)r.val(TOK0 + kHuffCtx + huff_cls(c + i));
-            c -= t;
-        } else if (t == 0) {
-            break;
-        } else {
-            if (t > nn - c) { r.bad = true; break; }
-            c += t;
-        }
-    }
 }
 
 // One thread per block, the frame's tables validated and expanded once per workgroup.
@@ -470,16 +388,7 @@ __global__ void __launch_bounds__(256) unpack_huff_block_kernel(const UnpackArgs
     zero_i16<BS * BS>(q);
     const int inter = f.frame_type == 1;
     HuffReader r(f.in + o0, o1 - o0, o1 < o0, tabs);
-    const int sp = r.split();
-    if (sp != 0 && BS != 16) r.bad = true;
-    f.split[b] = (uint8_t)(sp == 1 && !r.bad);
-    int16_t* mv = f.mv + (size_t)b * (inter ? 12 : 4);
-    const int per = inter ? 3 : 1, nmv = (sp == 1 ? 4 : 1) * per;
-    for (int j = 0; j < 4 * per; ++j) mv[j] = (int16_t)(j < nmv && !r.bad ? r.val(0) : 0);
-    const int nsub = sp == 1 ? 4 : 1, n = sp == 1 ? 8 : BS, nn = n * n;
-    const uint8_t* scan = scan_table(n);
-    for (int j = 0; j < nsub && !r.bad; ++j) unpack_huff_list<1>(q + j * nn, scan, nn, r);
-    r.finish();
+    unpack_huff_luma_record<BS>(r, inter, f.split + b, f.mv + (size_t)b * (inter ? 12 : 4), q);
     if (r.bad) __hip_atomic_store(err, b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -499,9 +408,7 @@ __global__ void __launch_bounds__(256) unpack_chroma_huff_kernel(const ChromaUnp
     zero_i16<64>(qu);
     zero_i16<64>(qv);
     HuffReader r(f.in + o0, o1 - o0, o1 < o0, tabs);
-    unpack_huff_list<0>(qu, scan_table(8), 64, r);
-    if (!r.bad) unpack_huff_list<0>(qv, scan_table(8), 64, r);
-    r.finish();
+    unpack_huff_chroma_record(r, qu, qv);
     if (r.bad) __hip_atomic_store(err, b + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 

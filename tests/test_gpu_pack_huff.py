@@ -299,6 +299,40 @@ def test_unpack_huff_single_block_mutants(gpu):
             assert np.array_equal(m[c, :12], res["mv"][0].reshape(-1))
 
 
+@pytest.mark.parametrize("kind", [0, 1])
+def test_unpack_huff_mutant_frames_agree_with_strict_model(gpu, kind):
+    """The table mutants (frames of 7 records) and a seeded sample of record mutants (frames of one
+    record) of packhuffcases.gpu_frames, one call and one err word per frame: err is 0 exactly when
+    the model accepts every record, else it names a record the model rejects -- record 0 for
+    malformed tables, and then nothing of the frame is written; every record the model accepts
+    decodes to the model's values whatever its neighbours; guard elements stay untouched."""
+    bs = (16, 8)[kind]
+    frames = C.gpu_frames(kind)
+    assert sum(all(v[0] == "ok" for v in f[4]) for f in frames) > 50 and sum(not f[3] for f in frames) > 50
+    for nb in sorted({len(f[2]) for f in frames}):
+        group = [f for f in frames if len(f[2]) == nb]
+        u = _Unpack(gpu, [b"".join(f[2]) for f in group], [_offsets(f[2]) for f in group], nb, bs, ncalls=len(group))
+        for c, f in enumerate(group):
+            u.launch([c], [f[1]], call=c)
+        s, m, q, err = u.fetch()
+        for c, (name, ft, recs, tables_ok, verdicts) in enumerate(group):
+            bad = {b for b, v in enumerate(verdicts) if v[0] == "bad"}
+            e = int(err[c])
+            assert (e == 0) == (not bad), (name, e, sorted(bad))
+            assert e == 0 or e - 1 in bad, (name, e, sorted(bad))
+            w = 12 if ft == 1 else 4
+            assert (s[c, nb:] == SPLIT_FILL).all() and (m[c, nb * w:] == I16_FILL).all(), name
+            assert (q[c, nb * bs * bs:] == I16_FILL).all(), name
+            if not tables_ok:
+                assert e == 1 and (s[c] == SPLIT_FILL).all() and (m[c] == I16_FILL).all() and (q[c] == I16_FILL).all(), name
+                continue
+            for b, (verdict, res) in enumerate(verdicts):
+                if verdict == "ok":
+                    assert s[c, b] == res[0], (name, b)
+                    assert np.array_equal(m[c, b * w:(b + 1) * w], res[1]), (name, b)
+                    assert np.array_equal(q[c, b * bs * bs:(b + 1) * bs * bs], res[2]), (name, b)
+
+
 # ---- the public paths --------------------------------------------------------------------------------
 def _rc_kw():
     import json

@@ -205,3 +205,29 @@ def test_unpack_chroma_huff_agrees_with_strict_model(gpu):
         if kind == "ok":
             assert np.array_equal(q[c, 0, :nb * 64].reshape(nb, 64), res["qtc_u"])
             assert np.array_equal(q[c, 1, :nb * 64].reshape(nb, 64), res["qtc_v"])
+
+
+def test_unpack_chroma_huff_mutant_frames_agree_with_strict_model(gpu):
+    """The table mutants (frames of 7 records) and a seeded sample of record mutants (frames of one
+    record) of packhuffcases.gpu_frames, one call and one err word per frame: err is 0 exactly when
+    the model accepts every record, else it names a record the model rejects -- record 0 for
+    malformed tables, and then nothing of the frame is written; every record the model accepts
+    decodes to the model's values; guard elements stay untouched."""
+    frames = C.gpu_frames(2)
+    assert sum(all(v[0] == "ok" for v in f[4]) for f in frames) > 50 and sum(not f[3] for f in frames) > 50
+    for nb in sorted({len(f[2]) for f in frames}):
+        group = [f for f in frames if len(f[2]) == nb]
+        q, err = _unpack(gpu, [b"".join(f[2]) for f in group], [_offsets(f[2]) for f in group], nb, ncalls=len(group))
+        for c, (name, _, recs, tables_ok, verdicts) in enumerate(group):
+            bad = {b for b, v in enumerate(verdicts) if v[0] == "bad"}
+            e = int(err[c])
+            assert (e == 0) == (not bad), (name, e, sorted(bad))
+            assert e == 0 or e - 1 in bad, (name, e, sorted(bad))
+            assert (q[c, :, nb * 64:] == I16_FILL).all(), name
+            if not tables_ok:
+                assert e == 1 and (q[c] == I16_FILL).all(), name
+                continue
+            for b, (verdict, res) in enumerate(verdicts):
+                if verdict == "ok":
+                    assert np.array_equal(q[c, 0, b * 64:(b + 1) * 64], res[2][:64]), (name, b)
+                    assert np.array_equal(q[c, 1, b * 64:(b + 1) * 64], res[2][64:]), (name, b)

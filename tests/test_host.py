@@ -260,6 +260,29 @@ def _unpack_check_cases():
     return cases
 
 
+_UNPACK_CHECK = []
+
+
+def _unpack_check_exe(tmp_path) -> str:
+    """tests/host/unpack_check.cpp built once per session, under both sanitizers."""
+    import shutil
+    import subprocess
+    if not _UNPACK_CHECK:
+        cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+        assert cxx is not None, "no host C++ compiler"
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        exe = str(tmp_path / "unpack_check")
+        subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                        "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-isystem", "/opt/rocm/include",
+                        os.path.join(root, "tests", "host", "unpack_check.cpp"), "-o", exe],
+                       check=True, capture_output=True)
+        _UNPACK_CHECK.append(exe)
+    return _UNPACK_CHECK[0]
+
+
+_OUT_REC = np.dtype([("bad", np.uint8), ("split", np.uint8), ("mv", np.int16, 12), ("q", np.int16, 256)])
+
+
 def test_unpack_record_bodies_under_sanitizers(tmp_path):
     """The strict decoders of streamoptima_amd/csrc/so_packfmt.h (the record bodies the unpack kernels
     run), compiled for the host with AddressSanitizer and UndefinedBehaviorSanitizer
@@ -267,17 +290,9 @@ def test_unpack_record_bodies_under_sanitizers(tmp_path):
     of exactly its size): on every corpus record and every mutant, in both codings, accept / reject
     and the decoded split, mv values and coefficients equal the strict models', and no access leaves
     a record's bytes or its outputs."""
-    import shutil
     import struct
     import subprocess
-    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx is not None, "no host C++ compiler"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "unpack_check")
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-isystem", "/opt/rocm/include",
-                    os.path.join(root, "tests", "host", "unpack_check.cpp"), "-o", exe],
-                   check=True, capture_output=True)
+    exe = _unpack_check_exe(tmp_path)
     cases = _unpack_check_cases()
     assert sum(c[4] is None for c in cases) > 1000 and sum(c[4] is not None for c in cases) > 1000
     assert {(c[0], c[1]) for c in cases} == {(a, b) for a in (0, 1) for b in (0, 1, 2)}
@@ -287,8 +302,7 @@ def test_unpack_record_bodies_under_sanitizers(tmp_path):
             f.write(struct.pack("<BBBBI", coding, kind, ftype, 0, len(data)) + data)
     r = subprocess.run([exe, src, dst], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    rec = np.dtype([("bad", np.uint8), ("split", np.uint8), ("mv", np.int16, 12), ("q", np.int16, 256)])
-    got = np.fromfile(dst, dtype=rec)
+    got = np.fromfile(dst, dtype=_OUT_REC)
     assert got.size == len(cases)
     for i, (coding, kind, ftype, data, want) in enumerate(cases):
         g = got[i]
@@ -298,3 +312,41 @@ def test_unpack_record_bodies_under_sanitizers(tmp_path):
             assert g["split"] == split, (i, coding, kind, ftype, data.hex())
             assert np.array_equal(g["mv"][:mv.size], mv) and not g["mv"][mv.size:].any(), (i, coding, kind, ftype)
             assert np.array_equal(g["q"][:q.size], q) and not g["q"][q.size:].any(), (i, coding, kind, ftype)
+
+
+def test_unpack_huff_record_bodies_under_sanitizers(tmp_path):
+    """The same program on coding 2 = huff: the table rule, HuffDec, HuffReader, the list parser and the
+    two record bodies of so_packfmt.h, the functions the huff unpack kernels call.  Every case of
+    tests/packhuffcases.py host_cases() -- the table bytes, the record's bytes, the expanded tables and
+    every output each in a heap allocation of exactly their size: accept / reject, split, mv values and
+    coefficients equal the strict model's (tests/packhuffref.py unpack_record_huff_strict) per record.
+    The counts are caps against an empty corpus: per kind more than 1,000 accepted and 1,000 rejected
+    records, and every rule the model can reject a record of that kind by."""
+    import struct
+    import subprocess
+    import packhuffcases as C
+    exe = _unpack_check_exe(tmp_path)
+    cases = C.host_cases()
+    want = [C.case_verdict(c) for c in cases]
+    for kind in (0, 1, 2):
+        mine = [w for c, w in zip(cases, want) if c[0] == kind]
+        assert sum(k == "ok" for k, _ in mine) > 1000 and sum(k == "bad" for k, _ in mine) > 1000, kind
+        assert {r for k, r in mine if k == "bad"} == set(C.REASONS[kind]), kind
+    src, dst = str(tmp_path / "huff_records.bin"), str(tmp_path / "huff_decoded.bin")
+    with open(src, "wb") as f:
+        for kind, ftype, tb, body, _ in cases:
+            f.write(struct.pack("<BBBBII", 2, kind, ftype, 0, len(body), len(tb)) + tb + body)
+    r = subprocess.run([exe, src, dst], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    got = np.fromfile(dst, dtype=_OUT_REC)
+    assert got.size == len(cases)
+    for g, (kind, ftype, tb, body, name), (verdict, res) in zip(got, cases, want):
+        where = (name, kind, ftype, tb[:8].hex(), body.hex())
+        assert bool(g["bad"]) == (verdict == "bad"), where
+        if verdict == "ok":
+            split, mv, q = res
+            assert g["split"] == split, where
+            assert np.array_equal(g["mv"][:mv.size], mv) and not g["mv"][mv.size:].any(), where
+            assert np.array_equal(g["q"][:q.size], q) and not g["q"][q.size:].any(), where
+        elif res in ("short tables", "spare nibble", "kraft"):
+            assert not g["split"] and not g["mv"].any() and not g["q"].any(), where     # nothing decoded

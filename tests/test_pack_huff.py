@@ -91,6 +91,36 @@ def test_length_limit_on_fibonacci_counts(monkeypatch):
     assert max(H.huffman_lengths([0] + fib[:21] + [fib[21] + nb * 224 - sum(fib[:22])] + [0] * 20)) == 21   # the limit did bind
 
 
+def test_huffman_rounds_counts_the_halvings():
+    fib = list(C.FIB)
+    for scale, rounds in ((1, 1), (2, 2), (4, 3)):
+        counts = [scale * c for c in fib] + [0] * 26
+        lens, got = H.huffman_rounds(counts)
+        assert got == rounds and lens == H.huffman_lengths(counts) == H.huffman_lengths(H.halved(counts, rounds))
+        assert H.huffman_rounds(H.halved(counts, rounds - 1))[1] == 1      # no round fewer would do
+    assert H.huffman_rounds(fib[:16] + [0] * 27) == (H.huffman_lengths(fib[:16] + [0] * 27), 0)
+    assert max(H.huffman_lengths(fib[:16] + [0] * 27)) == 15
+    assert H.huffman_rounds([0] * 43) == ([0] * 43, 0) and H.huffman_rounds([3] + [0] * 42) == ([1] + [0] * 42, 0)
+
+
+@pytest.mark.parametrize("name", C.LIMIT_NAMES)
+def test_limit_frames_design_and_round_trip(name):
+    """The frames designed to bind the 15-bit limit (packhuffcases.limit_frames): what each is for holds
+    by the model, and each round-trips through the model's strict decoder and the host decoder."""
+    C.check_limit_design(name)
+    for f, blocks in zip(C.limit_frames()[name], C.limit_model(name)):
+        whole = _u8(b"".join(blocks))
+        if f["kind"] == "chroma":
+            got = H.unpack_chroma_records_huff_strict(blocks)
+            assert np.array_equal(got["qtc_u"], f["qu"]) and np.array_equal(got["qtc_v"], f["qv"])
+            got = bitstream.unpack_chroma_frame_huff(whole, len(blocks))
+            assert np.array_equal(got["qtc_u"], f["qu"]) and np.array_equal(got["qtc_v"], f["qv"])
+        else:
+            assert _same_luma(H.unpack_blocks_huff_strict(blocks, f["bs"], f["ftype"]), f["split"], f["mv"], f["qtc"])
+            got = bitstream.unpack_frame_huff(whole, len(blocks), f["bs"], f["ftype"])
+            assert _same_luma(got, f["split"], f["mv"], f["qtc"])
+
+
 @pytest.mark.parametrize("name,ft", GOLDENS)
 def test_goldens_round_trip(name, ft):
     g = golden(name + ".npz")
