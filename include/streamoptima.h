@@ -763,6 +763,59 @@ int so_scale_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const ui
                     const int16_t* coef_cv, const int32_t* first_cv, int taps_cv, void* stream);
 
 /*
+ * Deblocking (build extension; DESIGN.md "Deblocking"): a display-side post-filter over the edges of
+ * the transform grid of decoded 8-bit 4:2:0 planes.  It is NOT in the coding loop: the sources (the
+ * reconstructions, which stay the references) are only read, separate planes are written.  Exact
+ * integers, >> the arithmetic shift (floor), one launch for Y, U and V of a batch of frames,
+ * asynchronous on `stream`, no host synchronisation, no allocation.  tests/deblockref.py restates it
+ * in numpy.
+ *   planes      dense H x W luma (H, W multiples of bs) and H/2 x W/2 chroma planes.  The whole padded
+ *               plane is filtered; callers crop afterwards.  Samples no edge touches are copied: the
+ *               output is a complete plane.
+ *   cells       every plane is a grid of 8 x 8 cells.  blockqp(b) = qp_map[b] if a map is given, else
+ *               qp_row[by] if rows are given, else qp, clamped to 0..20 (maps and rows are device
+ *               memory nobody validated: a bad entry gives a wrong picture and nothing worse).
+ *               Luma cell in block b: cellqp = blockqp(b), and where split[b] != 0, blockqp(b) - 1
+ *               (0 stays 0): the rule split sub-blocks are dequantised by.  bs 16: a block is 2 x 2
+ *               cells; bs 8: one cell.  Chroma cell, one per luma block:
+ *               cellqp = clamp(blockqp(b) + chroma_qp_offset, 0, 20); split does not enter.
+ *   edges       between two horizontally or vertically adjacent cells of a plane that belong to
+ *               different blocks, or (luma, bs 16) to one block with split[b] != 0.  None on the plane's
+ *               border.  q = clamp(max(cellqp_P, cellqp_Q) + strength, 0, 20), s = 1 << q,
+ *               alpha = min(s, 255), beta = min((3 * s) >> 3, 255), tc = min(s >> 2, 255),
+ *               tc1 = tc >> 1.  For q < 2, tc is 0 and the filter is the identity.
+ *   one line    across an edge, p2 p1 p0 | q0 q1 q2 with p0, q0 adjacent to it:
+ *                 d   = q0 - p0
+ *                 on  = |d| < alpha and |p1 - p0| < beta and |q1 - q0| < beta
+ *                 ap  = |p2 - p0| < beta            aq = |q2 - q0| < beta
+ *                 dl  = clip3(-tc, tc, (4 * d + (p1 - q1) + 4) >> 3)
+ *                 avg = (p0 + q0 + 1) >> 1                        (from the unfiltered p0, q0)
+ *                 if on:       p0' = clip(p0 + dl, 0, 255)    q0' = clip(q0 - dl, 0, 255)
+ *                 if on && ap: p1' = p1 + clip3(-tc1, tc1, (p2 + avg - 2 * p1) >> 1)
+ *                 if on && aq: q1' = q1 + clip3(-tc1, tc1, (q2 + avg - 2 * q1) >> 1)
+ *               p2 and q2 are never written; p1' and q1' stay inside 0..255 by construction.
+ *   order       pass 1 filters every vertical edge (lines along rows) from the input, pass 2 every
+ *               horizontal edge (lines along columns) from pass 1's result.  Inside a pass the edges
+ *               are independent: 8 apart, a line writes two samples a side and reads three.
+ *   arrays      sy .. dv, split, qp_row, qp_map: HOST arrays of nframes device pointers.  split (uint8
+ *               [nb]), qp_row (int32 [H / bs]) and qp_map (int32 [nb]) may be NULL as a whole or hold
+ *               NULL for single frames: no splits; no map -> rows -> qp.
+ *   luma only   su == sv == du == dv == NULL filters luma alone; a partial set is invalid.
+ * SO_E_INVALID before any launch, the argument named in so_last_error, in this order: nframes < 0; bs
+ * not 8 or 16; H or W not a positive multiple of bs, or H * W above 2^31 samples (one rule, the
+ * bound every frame geometry of this library has); qp outside 0..20; chroma_qp_offset outside
+ * -20..20; strength outside -3..3; (nframes == 0 returns SO_OK here;) sy or dy NULL or holding a NULL
+ * plane; a partial chroma set or a NULL chroma plane; a destination plane that overlaps a source or
+ * another destination of the call.  SO_E_UNSUPPORTED: chroma with bs 8; a non-NULL split entry with
+ * bs 8 (4-sample sub-blocks: the lines of a pass would overlap).
+ */
+int so_deblock_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const uint8_t* const* sv,
+                      int nframes, int H, int W, int bs, const uint8_t* const* split, int qp,
+                      const int32_t* const* qp_row, const int32_t* const* qp_map,
+                      int chroma_qp_offset, int strength,
+                      uint8_t* const* dy, uint8_t* const* du, uint8_t* const* dv, void* stream);
+
+/*
  * out[i] = sum of rows[i][0..len) (int32 -> int64) for i < n: the per-frame SSE of a GOP from
  * the encode kernels' per-block / per-row out_sse arrays (rows: a HOST array of device
  * pointers), one launch.

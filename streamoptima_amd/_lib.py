@@ -70,6 +70,7 @@ _SIGS = {
     "so_yuv420_to_rgb": ([_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _sz, _vp], _i),
     "so_scale_yuv420": ([_vp, _vp, _vp, _i, _i, _i, _sz, _sz, _vp, _vp, _vp, _i, _i, _i, _i,
                          _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp], _i),
+    "so_deblock_yuv420": ([_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp], _i),
     "so_block_xform": ([_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp], _i),
     "so_encode_p_run_stripe": ([_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _i, _vp, _vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, ctypes.c_uint32, _i, _vp], _i),

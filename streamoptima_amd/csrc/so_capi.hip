@@ -15,6 +15,7 @@
 #include "so_chroma.h"
 #include "so_colour.h"
 #include "so_common.h"
+#include "so_deblock.h"
 #include "so_launch.h"
 #include "so_packfmt.h"
 #include "so_run.h"
@@ -1256,6 +1257,102 @@ int so_scale_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const ui
                 p.d[k][i] = dsts[k][f0 + i];
             }
         SO_TRY(scale_launch(p, m, g, (hipStream_t)stream));
+    }
+    return SO_OK;
+}
+
+// ---- deblocking post-filter (so_deblock.hip) -----------------------------------------------------
+int so_deblock_yuv420(const uint8_t* const* sy, const uint8_t* const* su, const uint8_t* const* sv, int nframes,
+                      int H, int W, int bs, const uint8_t* const* split, int qp, const int32_t* const* qp_row,
+                      const int32_t* const* qp_map, int chroma_qp_offset, int strength, uint8_t* const* dy,
+                      uint8_t* const* du, uint8_t* const* dv, void* stream) {
+    const char* fn = "so_deblock_yuv420";
+    if (nframes < 0) {
+        set_error("%s: nframes %d", fn, nframes);
+        return SO_E_INVALID;
+    }
+    if (bs != 8 && bs != 16) {
+        set_error("%s: bs %d (the cells are 8 x 8: block size 8 or 16)", fn, bs);
+        return SO_E_INVALID;
+    }
+    if (H <= 0 || W <= 0 || H % bs || W % bs || (long long)H * W > (1ll << 31)) {
+        set_error("%s: H %d, W %d (positive multiples of bs %d, at most 2^31 samples)", fn, H, W, bs);
+        return SO_E_INVALID;
+    }
+    if (qp < 0 || qp > 20) {
+        set_error("%s: qp %d outside [0, 20]", fn, qp);
+        return SO_E_INVALID;
+    }
+    if (chroma_qp_offset < -20 || chroma_qp_offset > 20) {
+        set_error("%s: chroma_qp_offset %d outside [-20, 20]", fn, chroma_qp_offset);
+        return SO_E_INVALID;
+    }
+    if (strength < -3 || strength > 3) {
+        set_error("%s: strength %d outside [-3, 3]", fn, strength);
+        return SO_E_INVALID;
+    }
+    if (nframes == 0) return SO_OK;
+    SO_NEED(sy, fn); SO_NEED(dy, fn);
+    for (int i = 0; i < nframes; ++i)
+        if (!sy[i] || !dy[i]) {
+            set_error("%s: %s[%d] is NULL", fn, !sy[i] ? "sy" : "dy", i);
+            return SO_E_INVALID;
+        }
+    const int nchroma = (su != nullptr) + (sv != nullptr) + (du != nullptr) + (dv != nullptr);
+    if (nchroma != 0 && nchroma != 4) {
+        set_error("%s: %s is NULL (su, sv, du and dv are all given, or all NULL for luma only)", fn,
+                  !su ? "su" : !sv ? "sv" : !du ? "du" : "dv");
+        return SO_E_INVALID;
+    }
+    const bool chroma = nchroma == 4;
+    const uint8_t* const* srcs[3] = {sy, su, sv};
+    uint8_t* const* dsts[3] = {dy, du, dv};
+    static const char* const sname[3] = {"sy", "su", "sv"};
+    static const char* const dname[3] = {"dy", "du", "dv"};
+    for (int i = 0; chroma && i < nframes; ++i)
+        for (int k = 1; k < 3; ++k)
+            if (!srcs[k][i] || !dsts[k][i]) {
+                set_error("%s: %s[%d] is NULL", fn, !srcs[k][i] ? sname[k] : dname[k], i);
+                return SO_E_INVALID;
+            }
+    // A destination may share no byte with a source or another destination; sources may repeat.
+    std::vector<Span> spans;
+    spans.reserve((size_t)nframes * 6);
+    for (int i = 0; i < nframes; ++i)
+        for (int k = 0; k < (chroma ? 3 : 1); ++k) {
+            const size_t bytes = k ? (size_t)(H / 2) * (W / 2) : (size_t)H * W;
+            const uintptr_t ps = reinterpret_cast<uintptr_t>(srcs[k][i]), pd = reinterpret_cast<uintptr_t>(dsts[k][i]);
+            spans.push_back({ps, ps + bytes, false, sname[k], i});
+            spans.push_back({pd, pd + bytes, true, dname[k], i});
+        }
+    SO_TRY(check_spans(fn, spans, true));
+    if (chroma && bs == 8) {
+        set_error("%s: chroma needs bs 16 (the 4:2:0 codec is built for 16 x 16 blocks)", fn);
+        return SO_E_UNSUPPORTED;
+    }
+    for (int i = 0; bs == 8 && split && i < nframes; ++i)
+        if (split[i]) {
+            set_error("%s: split[%d] with bs 8 (4-sample sub-blocks: the lines of a pass would overlap)", fn, i);
+            return SO_E_UNSUPPORTED;
+        }
+
+    DeblockGeom g{};
+    g.H = H; g.W = W; g.bs = bs; g.nplanes = chroma ? 3 : 1;
+    g.qp = qp; g.chroma_qp_offset = chroma_qp_offset; g.strength = strength;
+    deblock_tiles(&g);
+    for (int f0 = 0; f0 < nframes; f0 += kDeblockBatch) {
+        const int m = nframes - f0 < kDeblockBatch ? nframes - f0 : kDeblockBatch;
+        DeblockPtrs p{};
+        for (int i = 0; i < m; ++i) {
+            for (int k = 0; k < g.nplanes; ++k) {
+                p.s[k][i] = srcs[k][f0 + i];
+                p.d[k][i] = dsts[k][f0 + i];
+            }
+            p.split[i] = split ? split[f0 + i] : nullptr;
+            p.qp_row[i] = qp_row ? qp_row[f0 + i] : nullptr;
+            p.qp_map[i] = qp_map ? qp_map[f0 + i] : nullptr;
+        }
+        SO_TRY(deblock_launch(p, m, g, (hipStream_t)stream));
     }
     return SO_OK;
 }

@@ -38,7 +38,7 @@ def _canon_frame(frame_type, mvs, residuals, bs):
 class decoder:
     def __init__(self, intra_mode, intra_dur, block_size, frames, height, width, Qp, nRefFrames, FMEEnable, lam,
                  VBSEnable, VBSoverlay=None, RCFlag=None, targetBR=None, frame_rate=30, qp_rate_tables=None,
-                 ParallelMode=0, device=None, chroma_subpel=False):
+                 ParallelMode=0, device=None, chroma_subpel=False, deblock=False, deblock_strength=0):
         self.intra_mode = intra_mode
         self.intra_dur = intra_dur
         self.block_size = block_size
@@ -56,6 +56,15 @@ class decoder:
         # vectors (DESIGN.md "Chroma with FMEEnable").  Like FMEEnable itself the precision is not in any
         # file: it is this argument, and it must be what the encoder was given
         self.chroma_subpel = bool(chroma_subpel)
+        # build extension: the display-side deblocking post-filter (DESIGN.md "Deblocking").  The frames
+        # every decode call returns and saves are filtered; the references stay the raw reconstructions,
+        # so the stream decodes as it always did.  deblock_strength (-3..3) shifts the filter's QP
+        if int(deblock_strength) < -3 or int(deblock_strength) > 3:
+            raise ValueError(f"deblock_strength {deblock_strength} outside [-3, 3]")
+        if deblock and block_size not in (8, 16):
+            raise NotImplementedError("deblock needs block_size 8 or 16")
+        self.deblock = bool(deblock)
+        self.deblock_strength = int(deblock_strength)
         self.lam = lam
         self.VBSEnable = VBSEnable
         self.VBSoverlay = VBSoverlay
@@ -103,11 +112,35 @@ class decoder:
                 refs_v.append(c.recon_v)
         return out
 
+    def _deblock_frames(self, eng, planes, splits, qp_rows, qp_maps, chroma=None, qp_offset=0):
+        """The display frames of a decoded sequence: one so_deblock_yuv420 launch over the luma planes
+        and, with `chroma` ([(U, V)] device planes), U and V.  The sources stay as they are (they are
+        the references).  Returns ([y], [(u, v)] or None)."""
+        n = len(planes)
+        if eng.bs == 8:
+            splits = None    # no VBS at block size 8: the flags are all zero, and the filter refuses them
+        rows = [r if (self._rc() and r is not None and len(r)) else None for r in qp_rows]
+        ys, uvs = eng.deblock_yuv420(planes, chroma, split=splits, qp=self.Qp, qp_rows=rows, qp_maps=qp_maps,
+                                     chroma_qp_offset=int(qp_offset), strength=self.deblock_strength)
+        return [ys[i] for i in range(n)], (None if chroma is None else [(uvs[i, 0], uvs[i, 1]) for i in range(n)])
+
     def decode_symbols(self, symbols, engine=None, chroma_symbols=None):
         """GOP decode straight from device symbols (the encoder's closed loop).  With
         chroma_symbols (the encoder's ChromaSymbols per frame) U and V are rebuilt too, into
-        self.decoded_chroma_device; the return value stays the luma planes."""
+        self.decoded_chroma_device; the return value stays the luma planes.  With deblock=True
+        both are the filtered display frames (the reference lists keep the raw reconstructions)."""
         eng = self._eng(engine)
+        out = self._decode_symbols(symbols, eng, chroma_symbols)
+        if self.deblock and out:
+            qo = chroma_symbols[0].qp_offset if chroma_symbols else 0
+            out, c = self._deblock_frames(eng, out, [s.split for s in symbols], [s.qp_row for s in symbols],
+                                          [s.extra.get("qp_map") for s in symbols],
+                                          self.decoded_chroma_device if chroma_symbols is not None else None, qo)
+            if c is not None:
+                self.decoded_chroma_device = c
+        return out
+
+    def _decode_symbols(self, symbols, eng, chroma_symbols=None):
         if chroma_symbols is not None:
             lum = [FrameSymbols(s.frame_type, s.split, s.mv, None, None, None, None, qp_rd=self.Qp,
                                 qp_row=s.qp_row if self._rc() else None,
@@ -135,14 +168,17 @@ class decoder:
         return out
 
     def decode(self, frame_type_seq, residual_file, Qp_per_row_per_frame, mv_file, intra_mode=None, intra_dur=None,
-               block_size=None, frames=None, width=None, height=None, save_decoded_frames=True, qp_maps=None):
+               block_size=None, frames=None, width=None, height=None, save_decoded_frames=True, qp_maps=None,
+               _filter=True):
         """decoder.py:487-545 with the per-frame lists of the encoded package.  qp_maps: per
-        frame per-block QPs (ROI / two-pass RC build extension) or None."""
+        frame per-block QPs (ROI / two-pass RC build extension) or None.  With deblock=True the raw
+        planes and their split flags and QPs are kept for decode_chroma, whose launch filters Y, U and
+        V together (_filter=False, decode_bitstream's: this call then leaves the filtering to it)."""
         bs = block_size or self.block_size
         frames = frames or self.frames
         eng = self._eng()
         ref_frames = [alloc_planes(1, eng.h, eng.w, eng.device, fill=128)[0]]
-        decoded = []
+        decoded, side = [], []
         for i in range(frames):
             ft = frame_type_seq[i]
             split, mv, qtc = _canon_frame(ft, mv_file[i], residual_file[i], bs)
@@ -159,10 +195,15 @@ class decoder:
             else:
                 rec = eng.recon_inter(ref_frames, split_d, mv_d, qtc_d, self.Qp, qp_row, qp_map_dev=qm)
             decoded.append(rec)
+            side.append((split_d, qp_row, qm))
             if i < frames - 1:
                 if len(ref_frames) >= self.nRefFrames:
                     ref_frames.pop(0)
                 ref_frames.append(rec)
+        self._raw_luma = (decoded, side) if self.deblock else None
+        if self.deblock and decoded and _filter:
+            decoded, _ = self._deblock_frames(eng, decoded, [t[0] for t in side], [t[1] for t in side],
+                                              [t[2] for t in side])
         host = [d.cpu().numpy()[: self.h_pixels, : self.w_pixels] for d in decoded]
         if save_decoded_frames:
             self.decoded_vid_f = True
@@ -173,11 +214,18 @@ class decoder:
                       chroma_qp_offset=0):
         """U and V of every frame from the package's per-frame lists: mv_file as decode() takes
         it (the luma motion), chroma_residuals[i] = (qtc_u, qtc_v) as int16 [nb, 64] arrays or the
-        package's "chroma approx residual" entry.  Returns per-frame (U, V) cropped to the picture."""
+        package's "chroma approx residual" entry.  Returns per-frame (U, V) cropped to the picture.
+        With deblock=True the filter's one launch covers Y, U and V, so decode() of the same frames
+        comes first (it keeps the raw luma planes); the filtered luma of that launch is kept in
+        self._display_luma (device planes)."""
         if self.FMEEnable and not self.chroma_subpel:
             raise NotImplementedError("chroma with FMEEnable is not built")
         if self.block_size != 16:
             raise NotImplementedError("chroma needs block_size 16")
+        raw = getattr(self, "_raw_luma", None)
+        if self.deblock and (raw is None or len(raw[0]) != len(frame_type_seq)):
+            raise ValueError("decode_chroma with deblock=True filters U and V in one launch with the luma planes "
+                             "decode() keeps: call decode() on the same frames first")
         eng = self._eng()
         syms, qtcs = [], []
         for i, ft in enumerate(frame_type_seq):
@@ -207,6 +255,10 @@ class decoder:
                             .to(eng.device))
             qtcs.append(tuple(pair))
         dev = self._chroma_loop(eng, syms, qtcs, int(chroma_qp_offset))
+        if self.deblock and dev:
+            planes, side = raw
+            self._display_luma, dev = self._deblock_frames(eng, planes, [t[0] for t in side], [t[1] for t in side],
+                                                           [t[2] for t in side], dev, int(chroma_qp_offset))
         h2, w2 = self.h_pixels // 2, self.w_pixels // 2
         self.decoded_chroma = [(u.cpu().numpy()[:h2, :w2], v.cpu().numpy()[:h2, :w2]) for u, v in dev]
         return self.decoded_chroma
@@ -262,13 +314,18 @@ class decoder:
             with open(qp_map_file) as f:
                 maps = [(_bs.parse_qp_map_line(line, qps[i] if self._rc() else None, self.Qp, self.num_blocks_per_row)
                          if line.strip() else None) for i, line in enumerate(f)]
+        chroma = chroma_residual_file is not None
         host = self.decode(ft, res, qps, mvs, intra_mode, intra_dur, bs, frames, width, height, save_decoded_frames,
-                           qp_maps=maps)
+                           qp_maps=maps, _filter=not chroma)     # with chroma one launch filters Y, U and V below
         if chroma_residual_file is not None:
             with open(chroma_residual_file) as f:
                 cres = [_bs.parse_chroma_residual_line(line) for line in f if line.strip()]
             n = len(host)
             self.decode_chroma(ft[:n], mvs[:n], cres[:n], qps[:n], qp_maps=maps, chroma_qp_offset=chroma_qp_offset)
+            if self.deblock and n:
+                host = [d.cpu().numpy()[: self.h_pixels, : self.w_pixels] for d in self._display_luma]
+                if save_decoded_frames:
+                    self.decoded_vid = host
         return host
 
     def decode_packed_file(self, path: str, save_decoded_frames=True):
@@ -300,10 +357,16 @@ class decoder:
                                 qp_row=s.qp_row if self._rc() else None,
                                 extra={"qp_map": s.extra["qp_map"]} if "qp_map" in s.extra else {}) for s in syms]
             dev = self._chroma_loop(eng, lum, qtcs, int(meta["chroma_qp_offset"]))
+        decoded = self._decode_symbols(syms, eng)
+        if self.deblock and decoded:
+            decoded, fdev = self._deblock_frames(eng, decoded, [s.split for s in syms], [s.qp_row for s in syms],
+                                                 [s.extra.get("qp_map") for s in syms], dev if chroma else None,
+                                                 int(meta["chroma_qp_offset"]) if chroma else 0)
+            dev = fdev if chroma else None
+        if chroma:
             h2, w2 = self.h_pixels // 2, self.w_pixels // 2
             self.decoded_chroma_device = dev
             self.decoded_chroma = [(u.cpu().numpy()[:h2, :w2], v.cpu().numpy()[:h2, :w2]) for u, v in dev]
-        decoded = self.decode_symbols(syms, eng)
         host = [d.cpu().numpy()[: self.h_pixels, : self.w_pixels] for d in decoded]
         if save_decoded_frames:
             self.decoded_vid_f = True
@@ -312,7 +375,7 @@ class decoder:
 
     def decode_packed_stream(self, path: str, out_path: str | None = None, consume=None, chunk: int = 2,
                              nbuf: int = 2, output: str = "yuv420", colour=None, output_size=None,
-                             scale: str = "lanczos3") -> dict:
+                             scale: str = "lanczos3", deblock=None, deblock_strength=None) -> dict:
         """decode_packed_file's frames without its footprint (hostdecode.HostStreamDecoder): the file
         is read as it goes, P-frames and chroma are decoded from the packed records straight to
         pixels (so_decode_p_frames, so_decode_chroma_frames; a "huff" file through the unpack and
@@ -325,29 +388,35 @@ class decoder:
         then raw RGB24 and the call consume(i, rgb) with rgb [h, w, 3]; a luma-only file raises
         ValueError.  output_size=(ho, wo) resamples every frame on the device to that size (`scale`:
         "bilinear", "bicubic" or "lanczos3") before it is converted or downloaded; the frames, the
-        file and the arrays consume receives then have that size.  The stream decoder is kept with
-        this instance.  Returns {"frames",
+        file and the arrays consume receives then have that size.  deblock / deblock_strength: the
+        deblocking post-filter for this stream (None: this decoder's own setting); the frames are
+        filtered on the device before they are resampled, converted or downloaded.  The stream decoder
+        is kept with this instance.  Returns {"frames",
         "frame_type", "coding", "layout"}."""
         from .colour import as_colour
         from .hostdecode import HostStreamDecoder
         if (out_path is None) == (consume is None):
             raise ValueError("decode_packed_stream: give out_path or consume")
+        deblock = self.deblock if deblock is None else bool(deblock)
+        strength = self.deblock_strength if deblock_strength is None else int(deblock_strength)
         key = (int(chunk), int(nbuf), output, as_colour(colour), None if output_size is None else tuple(output_size),
-               scale)
+               scale, deblock, strength)
         if getattr(self, "_stream_dec", None) is None or self._stream_dec[0] != key:
             self._stream_dec = (key, HostStreamDecoder(self, chunk=chunk, nbuf=nbuf, output=output, colour=colour,
-                                                       output_size=output_size, scale=scale))
+                                                       output_size=output_size, scale=scale, deblock=deblock,
+                                                       deblock_strength=strength))
         hs = self._stream_dec[1]
         if out_path is None:
             return hs.decode_file(path, consume)
         return hs.decode_to_rgb(path, out_path) if output == "rgb" else hs.decode_to_yuv(path, out_path)
 
     def decode_to_rgb(self, path: str, out_path: str, colour=None, chunk: int = 2, nbuf: int = 2, output_size=None,
-                      scale: str = "lanczos3") -> dict:
+                      scale: str = "lanczos3", deblock=None, deblock_strength=None) -> dict:
         """The packed file at `path` as raw RGB24 at picture size (or at output_size), frame after
         frame: decode_packed_stream with output="rgb"."""
         return self.decode_packed_stream(path, out_path=out_path, chunk=chunk, nbuf=nbuf, output="rgb", colour=colour,
-                                         output_size=output_size, scale=scale)
+                                         output_size=output_size, scale=scale, deblock=deblock,
+                                         deblock_strength=deblock_strength)
 
     def save_decoded_frames(self, filename="yuv/decoded_bitstream_frames.yuv"):
         if not self.decoded_vid_f:

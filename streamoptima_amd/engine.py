@@ -1001,6 +1001,71 @@ class Engine:
         _lib.check(rc, "so_scale_yuv420")
         return out_y, (out_uv if chroma else None)
 
+    # ---- deblocking post-filter (so_deblock.hip) ---------------------------------------------
+    def _deblock_side(self, items, n: int, dtype, numel: int, what: str):
+        """Per-frame device arrays of so_deblock_yuv420 (split, qp_rows, qp_maps) -> (pointer array or
+        None, the tensors kept alive).  items: None, a tensor [n, numel], or a sequence of n entries,
+        each None, a tensor of numel elements, or (int32 only) a sequence of ints."""
+        from .colour import _on
+        if items is None:
+            return None, []
+        ts = []
+        for t in list(items):
+            if t is not None and not isinstance(t, torch.Tensor):
+                if dtype != torch.int32:
+                    raise ValueError(f"deblock_yuv420 {what}: tensors of {dtype}, or None")
+                t = self.device_const_i32([int(v) for v in t])
+            if t is not None and (t.dtype != dtype or t.numel() != numel or not t.is_contiguous()
+                                  or not _on(t, self.device)):
+                raise ValueError(f"deblock_yuv420 {what}: contiguous {dtype} tensors of {numel} elements on "
+                                 f"{self.device}, or None")
+            ts.append(t)
+        if len(ts) != n:
+            raise ValueError(f"deblock_yuv420 {what}: {len(ts)} entries for {n} frames")
+        return _lib.ptr_array(ts), ts
+
+    def deblock_yuv420(self, y, uv, split=None, qp: int = 0, qp_rows=None, qp_maps=None, chroma_qp_offset: int = 0,
+                       strength: int = 0, out_y: torch.Tensor | None = None, out_uv: torch.Tensor | None = None):
+        """The display-side deblocking post-filter (include/streamoptima.h "Deblocking"): one
+        so_deblock_yuv420 launch on the current stream, no host synchronisation.  y: [F, H, W] or a
+        sequence of dense [H, W] planes (H, W multiples of the engine's block size: the padded planes
+        the decoder holds); uv: [F, 2, H/2, W/2] or a sequence of (u, v) pairs, None for luma only.
+        split: per frame the uint8 [nb] split flags or None (no block split); qp_rows / qp_maps: per
+        frame an int32 [H / bs] / [nb] device tensor or None (map, then rows, then `qp`).  The sources
+        are only read.  Returns (y [F, H, W], uv [F, 2, H/2, W/2] or None), written into out_y /
+        out_uv when given (exactly those shapes, no byte shared with a source)."""
+        from . import colour as _colour
+        ys = list(y)
+        n = len(ys)
+        chroma = uv is not None
+        h, w = (int(ys[0].shape[-2]), int(ys[0].shape[-1])) if n else (self.h, self.w)
+        if h <= 0 or w <= 0 or h % self.bs or w % self.bs:
+            raise ValueError(f"deblock_yuv420: {w}x{h} planes are not a positive multiple of block_size {self.bs}")
+        nb = (h // self.bs) * (w // self.bs)
+        psy = _colour.plane_pointers(ys, n, (h, w), self.device, "deblock_yuv420 y")
+        psu = psv = pdu = pdv = None
+        if chroma:
+            uvs = list(uv)
+            psu = _colour.plane_pointers([t[0] for t in uvs], n, (h // 2, w // 2), self.device, "deblock_yuv420 uv")
+            psv = _colour.plane_pointers([t[1] for t in uvs], n, (h // 2, w // 2), self.device, "deblock_yuv420 uv")
+        psplit, keep_s = self._deblock_side(split, n, torch.uint8, nb, "split")
+        prow, keep_r = self._deblock_side(qp_rows, n, torch.int32, h // self.bs, "qp_rows")
+        pmap, keep_m = self._deblock_side(qp_maps, n, torch.int32, nb, "qp_maps")
+        if out_y is None:
+            out_y = torch.empty((n, h, w), dtype=torch.uint8, device=self.device)
+        pdy = _colour.plane_pointers(out_y, n, (h, w), self.device, "deblock_yuv420 out_y")
+        if chroma:
+            if out_uv is None:
+                out_uv = torch.empty((n, 2, h // 2, w // 2), dtype=torch.uint8, device=self.device)
+            pdu = _colour.plane_pointers([t[0] for t in out_uv], n, (h // 2, w // 2), self.device, "deblock_yuv420 out_uv")
+            pdv = _colour.plane_pointers([t[1] for t in out_uv], n, (h // 2, w // 2), self.device, "deblock_yuv420 out_uv")
+        rc = self.lib.so_deblock_yuv420(psy, psu, psv, n, h, w, self.bs, psplit, int(qp), prow, pmap,
+                                        int(chroma_qp_offset), int(strength), pdy, pdu, pdv,
+                                        _lib.stream_handle(self.device))
+        _lib.check(rc, "so_deblock_yuv420")
+        del keep_s, keep_r, keep_m
+        return out_y, (out_uv if chroma else None)
+
     def sse_into(self, a: torch.Tensor, b: torch.Tensor, acc: torch.Tensor) -> None:
         """acc (uint64 view of an int64 device scalar) += sum((a-b)^2)."""
         rc = self.lib.so_sse_u8(a.data_ptr(), b.data_ptr(), a.numel(), acc.data_ptr(),

@@ -25,6 +25,11 @@ copy stream B brings down one [chunk, h, w, 3] buffer in place of the Y, U and V
 With output_size the compute stream first resamples the picture area of the unit's planes
 (so_scale_yuv420) into planes of exactly that size; those are what is converted or downloaded.
 
+With deblock (decoder(deblock=True)) every set also holds display planes for its unit.  The unit's
+frames are filtered into them on the compute stream behind their reconstruction (so_deblock_yuv420),
+and scaling, conversion and the download read the display planes; the ring below keeps the raw
+reconstructions, which stay the references.
+
 Reconstructions live in a ring of planes: a plane is written again only after its download
 event (the compute stream waits for it) and, by stream order, after its last use as a reference.
 """
@@ -56,7 +61,12 @@ class _Set:
         self.offs = torch.zeros((c, eng.nb + 1), dtype=torch.int32, device=dev)     # [:, 0] stays 0
         self.coffs = torch.zeros((c, eng.nb + 1), dtype=torch.int32, device=dev)
         self.err = torch.zeros((2, c), dtype=torch.int32, device=dev)               # luma row, chroma row
-        self.sy_d = self.suv_d = None
+        self.sy_d = self.suv_d = self.db_y = self.db_uv = None
+        if hs.deblock:
+            # the unit's display planes: the deblocked frames, which nothing predicts from
+            self.db_y = torch.empty((c, eng.h, eng.w), dtype=torch.uint8, device=dev)
+            if hs.chroma_ok:
+                self.db_uv = torch.empty((c, 2, eng.h // 2, eng.w // 2), dtype=torch.uint8, device=dev)
         if hs.out_hw:
             # the unit's planes at output size, resampled on the compute stream
             ho, wo = hs.out_hw
@@ -80,7 +90,7 @@ class _Set:
 
 class HostStreamDecoder:
     def __init__(self, dec, chunk: int = 2, nbuf: int = 2, fused: bool = True, output: str = "yuv420", colour=None,
-                 output_size=None, scale: str = "lanczos3"):
+                 output_size=None, scale: str = "lanczos3", deblock=None, deblock_strength=None):
         """dec: a `decoder` (its geometry, Qp, nRefFrames, RCFlag, FMEEnable).  chunk: P-frames
         per unit; nbuf: units in flight.  fused=False decodes P-frames and chroma with the unpack
         and reconstruction kernels on the one dense symbol set instead of the fused kernels (the
@@ -91,13 +101,22 @@ class HostStreamDecoder:
         the picture area of its planes to that size (so_scale_yuv420 with the `scale` filter:
         "bilinear", "bicubic" or "lanczos3") into planes of exactly that size, which are then converted
         (output="rgb": scale, then convert) or downloaded; a luma-only file scales luma alone.  None:
-        nothing is staged and nothing resampled.  Every device and page-locked buffer is allocated here."""
+        nothing is staged and nothing resampled.  deblock / deblock_strength (None: dec.deblock,
+        dec.deblock_strength): every unit's frames pass the deblocking post-filter (so_deblock_yuv420) on
+        the compute stream into display planes of the unit's set; those are then resampled, converted
+        or downloaded, and the reconstructions stay the references.  Off: no such plane exists and
+        nothing is launched.  Every device and page-locked buffer is allocated here."""
         if output not in ("yuv420", "rgb"):
             raise ValueError(f"output {output!r} (\"yuv420\" or \"rgb\")")
         self.output, self.colour = output, as_colour(colour)
         if output == "rgb" and (dec.h_pixels % 2 or dec.w_pixels % 2):
             raise ValueError(f"output=\"rgb\" needs an even picture size, got {dec.w_pixels}x{dec.h_pixels}")
         self.fused = bool(fused)
+        self.deblock = bool(getattr(dec, "deblock", False) if deblock is None else deblock)
+        self.deblock_strength = int(getattr(dec, "deblock_strength", 0) if deblock_strength is None
+                                    else deblock_strength)
+        if not -3 <= self.deblock_strength <= 3:
+            raise ValueError(f"deblock_strength {self.deblock_strength} outside [-3, 3]")
         self.out_hw = self.scale_plan = None
         if output_size is not None:
             from . import scale as _scale
@@ -269,6 +288,9 @@ class HostStreamDecoder:
                                            rows[j:j + 1], maps[j:j + 1], ps[j:j + 1], hdr, state, coding)
                     elif chroma:
                         self._dense_chroma(s, j, 1, cpacked[j], coffs[j], rows[j], maps[j], ps[j], hdr, state, suffix, sh)
+                    if self.deblock:                       # before the next unpack overwrites the flags
+                        self._deblock(s, j, outs[j:j + 1], ps[j:j + 1], [self.d_split], rows[j:j + 1],
+                                      maps[j:j + 1], chroma, hdr)
             else:
                 # While the list is short (after an I-frame, nRefFrames > 1) a stream of this
                 # project's encoder can name a reference past it: the encoder keeps its list across
@@ -300,15 +322,22 @@ class HostStreamDecoder:
             elif chroma and not self.fme:                  # under FME every frame went with its luma above
                 self._fused_chroma(s, 0, types, cpacked, coffs, list(self.split[:n]), list(self.mv[:n]), rows, maps,
                                    ps, hdr, state, coding)
+            src_uv = [self.cplanes[p] for p in ps] if chroma else None
+            if self.deblock:
+                if types[0] == 0:                          # the dense set still holds the I-frame's flags
+                    self._deblock(s, 0, outs, ps, [self.d_split], rows, maps, chroma, hdr)
+                elif fused and not self.fme:               # the fused P-frames' flags: one launch for the unit
+                    self._deblock(s, 0, outs, ps, list(self.split[:n]), rows, maps, chroma, hdr)
+                outs, src_uv = s.db_y[:n], (s.db_uv[:n] if chroma else None)
             if self.out_hw:
-                eng.scale_yuv420(outs, [self.cplanes[p] for p in ps] if chroma else None, self.scale_plan,
+                eng.scale_yuv420(outs, src_uv, self.scale_plan,
                                  src_hw=self.scale_plan.src_hw, out_y=s.sy_d[:n],
                                  out_uv=s.suv_d[:n] if chroma else None, out_hw=self.out_hw)
                 if self.output == "rgb":
                     eng.yuv420_to_rgb(s.sy_d[:n], s.suv_d[:n], *self.out_hw, self.colour, out=s.rgb_d[:n],
                                       plane_hw=self.out_hw)
             elif self.output == "rgb":
-                eng.yuv420_to_rgb(outs, [self.cplanes[p] for p in ps], self.dec.h_pixels, self.dec.w_pixels,
+                eng.yuv420_to_rgb(outs, src_uv, self.dec.h_pixels, self.dec.w_pixels,
                                   self.colour, out=s.rgb_d[:n])
             done = torch.cuda.Event()
             done.record(comp)
@@ -322,14 +351,24 @@ class HostStreamDecoder:
                     s.uv_h[:n].copy_(s.suv_d[:n], non_blocking=True)
             else:
                 for j, p in enumerate(ps):
-                    s.y_h[j].copy_(self.planes[p], non_blocking=True)
+                    s.y_h[j].copy_(outs[j], non_blocking=True)
                     if chroma:
-                        s.uv_h[j].copy_(self.cplanes[p], non_blocking=True)
+                        s.uv_h[j].copy_(src_uv[j], non_blocking=True)
             self.err_h[k].copy_(s.err, non_blocking=True)
             s.down = torch.cuda.Event()
             s.down.record(self.d2h)
         for p in ps:
             self.plane_ev[p] = s.down
+
+    def _deblock(self, s, j0, planes, ps, split, rows, maps, chroma, hdr) -> None:
+        """The reconstructions `planes` (ring planes ps) of frames j0.. of the unit through
+        so_deblock_yuv420 into the set's display planes, one launch on the compute stream."""
+        n = len(planes)
+        self.eng.deblock_yuv420(planes, [self.cplanes[p] for p in ps] if chroma else None,
+                                split=split if self.eng.bs == 16 else None, qp=int(self.dec.Qp), qp_rows=rows,
+                                qp_maps=maps, chroma_qp_offset=int(hdr["chroma_qp_offset"]) if chroma else 0,
+                                strength=self.deblock_strength, out_y=s.db_y[j0:j0 + n],
+                                out_uv=s.db_uv[j0:j0 + n] if chroma else None)
 
     def _fused_chroma(self, s, j0, types, cpacked, coffs, split, mv, rows, maps, ps, hdr, state, coding) -> None:
         """Frames j0.. of the unit through so_decode_chroma_frames (_ex under FME: Engine picks it),
